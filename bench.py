@@ -2,7 +2,14 @@
 """bench.py — throughput of the MI355X path tracer on BASELINE.json's headline metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: it sets up, runs the W warmup steps, keeps
+the same steps running untimed until the shader clock has settled (below), times the K steps,
+writes the last step's outputs if --dump-outputs is given, and prints the line. Everything else
+(the CPU baselines, the DrawTest legs, the end-to-end and launch-alone legs, with N > 1 the second
+exchange) runs only with --full.
 
 A step is one pass of the hot path over one batch: every rank renders its
 row-block-cyclic share of the config's W x H image at the config's spp (one kernel
@@ -22,10 +29,19 @@ Mray/s, the reference's own formula (src/cpu/main.cpp:188-189; rays counted as
 parallel.cpp:122,204). Inputs are resident in HBM (the scene is uploaded once); no
 host transfer is inside the timed region.
 
-Besides the timed region (unless --no-extra-legs; the DrawTest legs first, then the W warmup
-steps, then the end-to-end and launch-alone legs, then the K timed steps -- the ~35 launches of
-those legs hold the render's load while the power controller raises the shader clock, which
-otherwise ramps through a short timed region, profiles/r6_g):
+Under a render's load the power controller raises the shader clock over ~13 ms (~50 launches of
+config 2), which a short timed region right after the warmup would measure (profiles/r6_g). A
+plain run therefore repeats the same step untimed between the warmup and the timed steps until
+HOLD_SECONDS of load have passed (`clock_hold_steps` in the line; at most HOLD_MAX_STEPS, two
+steps where a step is long); --no-extra-legs leaves that out too (counter passes).
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller, as float
+arrays a second build can be compared with (dump_outputs below): frame_rgb.npy, rays_per_step.npy.
+
+With --full, besides the timed region (the DrawTest legs first, then the W warmup
+steps, then the end-to-end and launch-alone legs, then the K timed steps -- the launches of
+those legs hold the render's load while the shader clock rises, in place of the plain run's
+untimed steps):
   * `ms_per_launch_alone`: the same launches one at a time on one stream, each kernel
     bracketed by HIP events the library records on that stream right around it
     (lrt_kernel_timing) -- the duration the roofline objects divide by; `ms_per_call_alone`:
@@ -72,6 +88,19 @@ FP32_PEAK_T = 157.3              # MI355X_MICROARCH.md: peak FP32 (vector), TFLO
 # one per sphere of the linear scan) + ~60 of shading = 213 for the reference's 9-sphere scene
 ALG_FLOP_PER_SPHERE, ALG_FLOP_SHADING = 17, 60
 PMC_INDEX = os.path.join(ROOT, "profiles", "pmc_index.json")
+# a plain run's untimed steps between warmup and timed region: until this much load has passed
+HOLD_SECONDS = 0.025
+HOLD_MAX_STEPS = 126             # chunks of 2, 4, ... 64 steps (config 2: ~26 ms)
+DUMP_MAX_PIXELS = 1 << 21        # --dump-outputs: larger frames are sampled (12 + 8 B per pixel kept)
+DUMP_SEED = 20240607
+
+
+PLAIN_TIMING_NOTE = ("ms_per_step: the K timed steps, pipelined over the render streams (a step's launch "
+                     "overlaps its neighbours' tails). Order: W warmup steps (ms_per_step_warmup; first launches "
+                     "record the tile order), clock_hold_steps untimed steps of the same render (until "
+                     f"{HOLD_SECONDS * 1e3:.0f} ms of load: under it the shader clock rises from ~2.18 to ~2.39 GHz "
+                     "over ~50 launches at constant cycles per wave, profiles/r6_g; none with --no-extra-legs), "
+                     "then the K timed steps. --full adds the launch-alone, end-to-end, DrawTest and CPU legs")
 
 
 def log(*a):
@@ -268,6 +297,30 @@ def read_pmc(key: str):
         return None
 
 
+def dump_outputs(outdir, frame_rgb, rays_per_step):
+    """--dump-outputs: frame_rgb [rows, W, 3] (a torch tensor: the RGB the last timed step left in
+    its caller's buffer -- the render never writes alpha) as outdir/frame_rgb.npy, float32. A frame
+    of more than DUMP_MAX_PIXELS pixels is sampled: that many pixel indices drawn once from a
+    fixed seed (sorted, the same for every run of the same shape), frame_rgb.npy [n, 3] and
+    frame_rgb_index.npy [n] (row * W + column, float64). rays_per_step.npy: [1] float64, the
+    counted rays of one timed step (all ranks). Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    rows, w = int(frame_rgb.shape[0]), int(frame_rgb.shape[1])
+    arrays = {}
+    if rows * w > DUMP_MAX_PIXELS:
+        import torch
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows * w, DUMP_MAX_PIXELS, replace=False))
+        frame_rgb = frame_rgb.reshape(rows * w, 3)[torch.from_numpy(idx).to(frame_rgb.device)]
+        arrays["frame_rgb_index"] = idx.astype(np.float64)
+    arrays["frame_rgb"] = np.ascontiguousarray(frame_rgb.cpu().numpy(), dtype=np.float32)
+    arrays["rays_per_step"] = np.array([rays_per_step], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def base_line(args, world, cfg):
     """The fields every line carries, the failure lines included (value null)."""
     return {"metric": METRIC, "value": None, "unit": "Mray/s", "n_gpus": world, "steps": args.steps,
@@ -356,9 +409,16 @@ def main():
     ap.add_argument("--shard-of", type=int, default=1,
                     help="diagnostic (1 process): render only rank 0's shard of an N-GPU run, no gather -- "
                          "the per-GPU render at N GPUs, measured on one")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baselines, the DrawTest legs, "
+                         "the end-to-end and launch-alone legs, with N > 1 the second exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy "
+                         "(frame_rgb, rays_per_step; float32 / float64, a seeded sample of a large frame)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="only the timed region (profiling runs): no launch-alone, end-to-end or CPU legs")
+                    help="only the warmup and the timed region (profiling runs): none of --full's legs, and "
+                         "no untimed clock-hold steps either")
     ap.add_argument("--cpu-budget", type=float, default=None, help="seconds of all-core CPU-baseline timing")
     ap.add_argument("--scene-global", action="store_true", help="read spheres from global memory, not LDS")
     ap.add_argument("--exchange", choices=["remote", "rccl"], default="remote",
@@ -390,7 +450,8 @@ def main():
             print(json.dumps(line), flush=True)
         log(f"error: WORLD_SIZE={world} but --gpus {args.gpus}")
         sys.exit(2)
-    extra = not args.no_extra_legs
+    extra = args.full and not args.no_extra_legs
+    hold = not args.full and not args.no_extra_legs
     wd = Watchdog(rank, world, base_line(args, world, cfg))
 
     # CPU baselines first: rank 0 at N=1 only, before anything touches the GPU.
@@ -649,9 +710,46 @@ def main():
             dist.barrier()
         return t1 - t0, float(rays.item())
 
+    def hold_clock(mode):
+        """A plain run's untimed steps of `mode` after the warmup: chunks of 2, 4, ... 64 steps, each
+        drained, until HOLD_SECONDS have passed on the slowest rank (every rank runs the same
+        count). Returns the steps run."""
+        wd.enter(f"clock_hold_{mode}")
+        n, chunk = 0, 2
+        sync_all()
+        t0 = time.perf_counter()
+        while n < HOLD_MAX_STEPS:
+            for k in range(chunk):
+                step(warmup + n + k, mode)
+            drain()
+            torch.cuda.synchronize()
+            n, chunk = n + chunk, chunk * 2
+            t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64,
+                             device=dev if backend == "nccl" else "cpu")
+            if world > 1:
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            if float(t[0]) >= HOLD_SECONDS:
+                break
+        sync_all()
+        return n
+
+    def last_frame_rgb(mode):
+        """The RGB of the frame the last timed step of `mode` produced, as its caller holds it: rank
+        0's assembled frame at N > 1 (every rank's stores have landed: timed() ends in a barrier),
+        the render's buffer at N = 1 (--shard-of: the shard). None on the other ranks."""
+        slot = (warmup + args.steps - 1) % nslots
+        if rank != 0:
+            return None
+        if mode == "remote":
+            return shared.tensor(slot)[..., :3]
+        if mode == "rccl":
+            return frames_out[slot][..., :3]
+        return bufs[slot][:rows, :, :3]
+
     mode = ("remote" if remote else "rccl") if world > 1 else "local"
     warmup_steps(mode)
     remote = mode == "remote"
+    hold_steps = hold_clock(mode) if hold else 0
     # ---- extra legs, BEFORE the timed region: end to end (D2H included), then each launch alone
     # (the roofline's duration). Under a render's full load the shader clock starts near 2.18 GHz
     # and the power controller raises it to ~2.39 GHz over ~50 launches (~13 ms); the cycles per
@@ -741,6 +839,9 @@ def main():
         {"e2e": leg_end_to_end, "alone": leg_alone}[leg]()
     elapsed, timed_rays = timed(mode)
     launch_info = L.last_launch()
+    dump_rgb = None
+    if args.dump_outputs and rank == 0:   # taken now: --full's later legs reuse the buffers
+        dump_rgb = last_frame_rgb(mode).contiguous().clone()
     for leg in legs[legs.index("timed") + 1:]:
         {"e2e": leg_end_to_end, "alone": leg_alone}[leg]()
     exchange_legs = None
@@ -865,6 +966,11 @@ def main():
                      "frac": round(alg_step / peak_all, 4), "duration_ms": round(ms_step, 4),
                      "note": "213 FLOP per counted ray x rays per step (all ranks) / ms_per_step (pipelined "
                              "timed region), against the FP32 vector peak of the n_gpus GPUs"}
+        dumped = None
+        if dump_rgb is not None:
+            wd.enter("dump_outputs")
+            dumped = dump_outputs(args.dump_outputs, dump_rgb, rays_per_step)
+            log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
         out = {
             "metric": METRIC,
             "value": round(value, 3),
@@ -877,7 +983,10 @@ def main():
             "ms_per_call_alone": round(call_ms, 4) if call_ms else None,
             "alone_launches": alone_n if alone_ms else None,
             "ms_per_step_warmup": round(warm[mode], 4),
-            "timing_note": "ms_per_step: the K timed steps, pipelined over the render streams (a step's launch "
+            "clock_hold_steps": hold_steps,
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
+            "timing_note": PLAIN_TIMING_NOTE if not extra else "ms_per_step: the K timed steps, pipelined over the render streams (a step's launch "
                            "overlaps its neighbours' tails); ms_per_launch_alone: one launch with nothing beside "
                            "it, the roofline's duration; ms_per_step_warmup: rank 0's W untimed warmup steps (first "
                            "launches record the tile order). Order: W warmup steps, the end_to_end and launch-alone "

@@ -61,3 +61,48 @@ def test_default_steps_give_a_long_timed_region():
     approx_ms = {2: 0.22, 3: 1.8, 4: 84.0, 5: 1370.0}
     for c, ms in approx_ms.items():
         assert bench.DEFAULT_STEPS[c] * ms >= 40.0, c
+
+
+def test_dump_outputs_small_frame_is_written_whole(tmp_path):
+    """--dump-outputs: a frame of at most DUMP_MAX_PIXELS pixels is written whole, float32, with
+    the step's ray count as float64."""
+    import numpy as np
+    import torch
+    rgb = torch.arange(5 * 7 * 3, dtype=torch.float32).reshape(5, 7, 3) / 8
+    shapes = bench.dump_outputs(str(tmp_path / "d"), rgb, 1234.0)
+    assert shapes == {"frame_rgb": [5, 7, 3], "rays_per_step": [1]}
+    got = np.load(tmp_path / "d" / "frame_rgb.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rgb.numpy())
+    rays = np.load(tmp_path / "d" / "rays_per_step.npy")
+    assert rays.dtype == np.float64 and rays.tolist() == [1234.0]
+
+
+def test_dump_outputs_samples_a_large_frame_the_same_way_every_time(tmp_path):
+    """A frame of more than DUMP_MAX_PIXELS pixels: a fixed, seeded, sorted sample of distinct
+    pixels, identical from call to call, the values those pixels hold, under 64 MB in all."""
+    import numpy as np
+    import torch
+    rows, w = 1025, 2048 + 3   # odd sizes, just above the threshold
+    assert rows * w > bench.DUMP_MAX_PIXELS
+    rgb = torch.arange(rows * w, dtype=torch.float32).reshape(rows, w, 1).expand(rows, w, 3).contiguous()
+    rgb[..., 1] += 0.5
+    a = bench.dump_outputs(str(tmp_path / "a"), rgb, 1.0)
+    b = bench.dump_outputs(str(tmp_path / "b"), rgb, 1.0)
+    assert a == b == {"frame_rgb_index": [bench.DUMP_MAX_PIXELS], "frame_rgb": [bench.DUMP_MAX_PIXELS, 3],
+                      "rays_per_step": [1]}
+    idx = np.load(tmp_path / "a" / "frame_rgb_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_rgb_index.npy"))
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < rows * w
+    got = np.load(tmp_path / "a" / "frame_rgb.npy")
+    assert got.dtype == np.float32
+    assert np.array_equal(got[:, 0], idx.astype(np.float32)) and np.array_equal(got[:, 1], got[:, 0] + 0.5)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 * 1000 * 1000
+
+
+def test_full_is_off_by_default_and_gates_every_extra_leg():
+    """A plain run times only the headline figure: every other leg hangs on --full."""
+    src = open(bench.__file__).read()
+    assert 'ap.add_argument("--full", action="store_true"' in src
+    assert "extra = args.full and not args.no_extra_legs" in src
+    assert "hold = not args.full and not args.no_extra_legs" in src

@@ -6,8 +6,8 @@
 # Steps (each under its own timeout; the session stops at the first failure):
 #   test[=K]          pytest -m gpu (optionally -k K)
 #   smoke             __graft_entry__.smoke()
-#   bench=C[,ARGS]    bench.py --config C (ARGS: extra bench flags, ';'-separated)
-#   trace=C[,ARGS]    rocprofv3 --kernel-trace --stats of bench.py --config C --streams 1
+#   bench=C[,ARGS]    bench.py --full --config C: every leg (ARGS: extra bench flags, ';'-separated)
+#   trace=C[,ARGS]    rocprofv3 --kernel-trace --stats of bench.py --full --config C --streams 1
 #   pmc=C,GROUP[,ARGS] one rocprofv3 --pmc pass (GROUP: fetch | write | sq | sq2 | cache) of bench --config C
 #   py=SCRIPT[,ARGS]  python SCRIPT ARGS (diagnostics under tools/; NAME=VALUE tokens set the environment)
 #   ab=V,C[,ARGS]     bench.py --config C with LRT_LIB=build_exp/liblrt_V.so (tools/build_variant.sh),
@@ -57,9 +57,9 @@ for s in "$@"; do
         run "test$i" 1100 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread
       fi ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) TAILN=1 run "bench_c${c}_$i" 600 python bench.py --config "$c" "${STEPARG[@]}" $extra ;;
+    bench) TAILN=1 run "bench_c${c}_$i" 600 python bench.py --full --config "$c" "${STEPARG[@]}" $extra ;;
     trace) run "trace_c${c}_$i" 600 rocprofv3 --kernel-trace --stats -d "$out" -o "trace_c${c}" --output-format csv -- \
-             python3 bench.py --config "$c" "${STEPARG[@]}" --streams 1 --no-cpu-baseline $extra ;;
+             python3 bench.py --full --config "$c" "${STEPARG[@]}" --streams 1 --no-cpu-baseline $extra ;;
     pmc)   g=${rest%%,*}
            pextra=""
            [[ "$rest" == *,* ]] && pextra=${rest#*,}
