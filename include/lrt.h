@@ -296,6 +296,54 @@ int lrt_unshard_rows_rgb(const float* d_src_rgb, float* d_dst, int width, int he
  * d_rgba (width*height*4 floats) -> d_bgra (width*height uint32, b | g<<8 | r<<16). */
 int lrt_present_bgra8(const float* d_rgba, uint32_t* d_bgra, int width, int height, void* stream);
 
+/* ---- denoiser ---------------------------------------------------------------- */
+
+/* Feature-guided denoiser for a rendered frame: an edge-avoiding a-trous wavelet filter
+ * (Dammertz et al. 2010) over the guides lrt_render_device_ex / lrt_render_host_ex produce,
+ * its colour weight scaled by the centre pixel's colour standard deviation (as in SVGF).
+ * `iterations` passes k = 0 .. iterations - 1 with the 5x5 B3-spline taps
+ * q = p + 2^k * (i, j), i, j in -2..2, h = [1/16, 1/4, 3/8, 1/4, 1/16]; taps outside the
+ * image are skipped:
+ *     c_{k+1}(p) = sum_q w(p,q) c_k(q) / sum_q w(p,q)                     (rgb only)
+ *     w(p,q) = h[i] h[j] exp(-E(p,q))
+ *     E = |c_k(p) - c_k(q)|^2 / ((sigma_color 2^-k)^2 |std(p)|^2 + 1e-6)   if color_std is given
+ *       + |n(p) - n(q)|^2 / sigma_normal^2                                 if normal is given
+ *       + |x(p) - x(q)|^2 / sigma_pos^2                                    if world_pos is given
+ *       + |a(p) - a(q)|^2 / sigma_albedo^2                                 if albedo is given
+ * (|.|^2: the squared rgb distance; the guides are the input buffers, unchanged over the
+ * passes). f32 throughout, deterministic run to run; tolerance-checked against its NumPy
+ * restatement (tests/denoise_ref.py), not bit-pinned: the reference has no such filter.
+ *
+ * Whole frames only: every buffer is height rows of width RGBA float quads. A
+ * row-block-cyclic shard (row_period > 1) lacks its rows' neighbours and cannot be filtered
+ * on its own -- assemble the frame first. No temporal reuse, no albedo demodulation, and the
+ * variance guide itself is not filtered. */
+#define LRT_DENOISE_MAX_ITER 5
+typedef struct lrt_denoise_desc {
+    int32_t width, height;      /* a whole frame: height rows of width RGBA float quads */
+    int32_t iterations;         /* 1..LRT_DENOISE_MAX_ITER */
+    int32_t flags;              /* 0 */
+    float sigma_color, sigma_normal, sigma_pos, sigma_albedo;   /* finite, > 0 */
+} lrt_denoise_desc;
+
+/* The defaults for a width x height frame: 5 iterations, sigma_color 2, sigma_normal 0.3,
+ * sigma_pos 0.5, sigma_albedo 0.2. */
+int lrt_denoise_default(int width, int height, lrt_denoise_desc* out);
+
+/* Filter d_color into d_out (device buffers). Of d_guides, normal, world_pos, albedo and
+ * color_std are read (a NULL member drops its term; without color_std there is no colour
+ * term); the other members and max_frame are ignored; d_guides == NULL means no guides.
+ * d_out may be d_color (in place) but not one of the guide buffers (LRT_E_INVALID); only its
+ * rgb is written, its alpha stays. No input is written when d_out != d_color. Asynchronous on
+ * `stream` and ordered only against it, like lrt_render_device; the intermediate passes live
+ * in that stream's scratch of the library. Acts on the first device. */
+int lrt_denoise_device(const lrt_denoise_desc* desc, const float* d_color, const lrt_features* d_guides,
+                       float* d_out, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; the output equals
+ * lrt_denoise_device's bit for bit. */
+int lrt_denoise_host(const lrt_denoise_desc* desc, const float* color, const lrt_features* guides, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,16 @@ class Features(ctypes.Structure):             # lrt_features (fragmentShader.fs.
 
 
 FEATURE_NAMES = ("normal", "world_pos", "albedo", "color_std", "normal_std", "world_pos_std")
+GUIDE_NAMES = ("normal", "world_pos", "albedo", "color_std")   # what lrt_denoise_* reads of lrt_features
+DENOISE_MAX_ITER = 5
+
+
+class DenoiseDesc(ctypes.Structure):          # lrt_denoise_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("iterations", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_pos", ctypes.c_float), ("sigma_albedo", ctypes.c_float)]
+
 
 _c = ctypes
 _vp = ctypes.c_void_p
@@ -130,6 +140,9 @@ SIGNATURES = {
     "lrt_pack_rgb": (_i, [_vp, _vp, _c.c_longlong, _vp]),
     "lrt_unshard_rows_rgb": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "lrt_present_bgra8": (_i, [_vp, _vp, _i, _i, _vp]),
+    "lrt_denoise_default": (_i, [_i, _i, _c.POINTER(DenoiseDesc)]),
+    "lrt_denoise_device": (_i, [_c.POINTER(DenoiseDesc), _vp, _c.POINTER(Features), _vp, _vp]),
+    "lrt_denoise_host": (_i, [_c.POINTER(DenoiseDesc), _vp, _c.POINTER(Features), _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

@@ -9,6 +9,7 @@
 //   lrt_hostpath.hip  host backbuffers: DrawTest's pipelined path, its look-ahead, staging
 //   lrt_multi.hip     one process, several devices: split, RCCL gather, IPC frames
 //   lrt_frame.hip     frame assembly and present kernels
+//   lrt_denoise.hip   the feature-guided a-trous denoiser (lrt_denoise_*): kernel and entry points
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
 #pragma once

@@ -284,6 +284,119 @@ def present_tensor(rgba, bgra, width: int, height: int, stream=None) -> None:
                                       int(width), int(height), ctypes.c_void_p(s.cuda_stream)))
 
 
+def render_tensor_features(job: Job, buf, rays, features: dict, max_frame: int = 4, stream=None) -> None:
+    """torch front end of lrt_render_device_ex: render_tensor plus the first-hit features.
+    `features` maps names of lrt_features to cuda float32 tensors shaped like buf, updated in
+    place for frames <= max_frame (< 0: all), so that render -> denoise -> present stays on
+    the device."""
+    import torch
+
+    d = job.desc()
+    need = d.row_count * d.x_count * 4
+    if not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous() and buf.numel() >= need):
+        raise L.LrtError(L.LRT_E_INVALID, f"buf must be a contiguous cuda float32 tensor of >= {need} elements")
+    if not (rays.is_cuda and rays.dtype == torch.int64 and rays.numel() >= 1):
+        raise L.LrtError(L.LRT_E_INVALID, "rays must be a cuda int64 tensor")
+    f = _tensor_features(features, need, L.FEATURE_NAMES, buf.device)
+    f.max_frame = int(max_frame)
+    s = stream if stream is not None else torch.cuda.current_stream(buf.device)
+    L.check(L.lib().lrt_render_device_ex(ctypes.byref(d), ctypes.c_void_p(buf.data_ptr()),
+                                         ctypes.c_void_p(rays.data_ptr()), ctypes.byref(f),
+                                         ctypes.c_void_p(s.cuda_stream)))
+
+
+# ---- denoiser ---------------------------------------------------------------------------
+def denoise_desc(width: int, height: int, **params) -> L.DenoiseDesc:
+    """lrt_denoise_default for a width x height frame, with any of iterations, sigma_color,
+    sigma_normal, sigma_pos, sigma_albedo overridden."""
+    d = L.DenoiseDesc()
+    L.check(L.lib().lrt_denoise_default(int(width), int(height), ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in ("iterations", "sigma_color", "sigma_normal", "sigma_pos", "sigma_albedo"):
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown denoise parameter {name!r}")
+        setattr(d, name, int(v) if name == "iterations" else float(v))
+    return d
+
+
+def _frame_size(color, params: dict):
+    """(width, height) of a [height, width, 4] frame, or the width= / height= given for a flat one."""
+    w, h = params.pop("width", None), params.pop("height", None)
+    if w is None or h is None:
+        if len(color.shape) != 3 or color.shape[2] != 4:
+            raise L.LrtError(L.LRT_E_INVALID, "color must be [height, width, 4], or pass width= and height=")
+        h, w = int(color.shape[0]), int(color.shape[1])
+    return int(w), int(h)
+
+
+def denoise_host(color: np.ndarray, guides: Optional[dict], out: Optional[np.ndarray] = None, **params):
+    """Filter a rendered frame with the feature-guided a-trous denoiser (lrt_denoise_host).
+    color: float32 [height, width, 4] (or flat with width=, height=); guides: {name: buffer}
+    with the lrt_features names "normal", "world_pos", "albedo", "color_std" (a missing one
+    drops its term; None or {}: no guides), as render_host_features fills them. out: the
+    destination (may be color; only its rgb is written), default a copy of color. params:
+    iterations, sigma_color, sigma_normal, sigma_pos, sigma_albedo. Returns out."""
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = denoise_desc(w, h, **params)
+    n = w * h * 4
+    _check_host_buffer(color, n)
+    if out is None:
+        out = color.copy()
+    _check_host_buffer(out, n)
+    f = L.Features()
+    for name, buf in (guides or {}).items():
+        if name not in L.GUIDE_NAMES:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown guide {name!r}")
+        _check_host_buffer(buf, n)
+        setattr(f, name, buf.ctypes.data)
+    L.check(L.lib().lrt_denoise_host(ctypes.byref(d), color.ctypes.data_as(ctypes.c_void_p),
+                                     ctypes.byref(f) if guides else None, out.ctypes.data_as(ctypes.c_void_p)))
+    return out
+
+
+def denoise_tensor(color, guides: Optional[dict], out=None, stream=None, **params):
+    """denoise_host on cuda float32 tensors (lrt_denoise_device): asynchronous on `stream` (a
+    torch.cuda.Stream, default: current) and ordered only against it. Returns out."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = denoise_desc(w, h, **params)
+    n = w * h * 4
+    s = stream if stream is not None else torch.cuda.current_stream(color.device)
+
+    def ok(t):
+        return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n
+
+    if not ok(color):
+        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
+    if out is None:
+        with torch.cuda.stream(s):
+            out = color.clone()
+    if not ok(out):
+        raise L.LrtError(L.LRT_E_INVALID, f"out must be a contiguous cuda float32 tensor of >= {n} elements")
+    f = _tensor_features(guides or {}, n, L.GUIDE_NAMES, color.device)
+    L.check(L.lib().lrt_denoise_device(ctypes.byref(d), ctypes.c_void_p(color.data_ptr()),
+                                       ctypes.byref(f) if guides else None, ctypes.c_void_p(out.data_ptr()),
+                                       ctypes.c_void_p(s.cuda_stream)))
+    return out
+
+
+def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
+    """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
+    import torch
+
+    f = L.Features()
+    for name, t in tensors.items():
+        if name not in names:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown feature {name!r}")
+        if not (t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous()
+                and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a contiguous cuda float32 tensor of >= {n} elements")
+        setattr(f, name, t.data_ptr())
+    return f
+
+
 def _check_host_buffer(buf: np.ndarray, n: int) -> None:
     if not isinstance(buf, np.ndarray) or buf.dtype != np.float32 or not buf.flags.c_contiguous or buf.size < n:
         raise L.LrtError(L.LRT_E_INVALID, f"backbuffer must be a C-contiguous float32 array of >= {n} elements")

@@ -1,0 +1,173 @@
+"""The denoiser's host-side contract (no GPU): argument validation and defaults of the C-ABI
+(lrt_denoise_*), and the specified filter itself -- its NumPy restatement (tests/denoise_ref.py)
+on the oracle's 4 spp render with features against the oracle's 1024 spp render, plus sanity
+checks of the restatement the GPU tests compare the kernel with."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import denoise_ref as R
+import oracle
+from learnraytracing_amd import _lib as L
+
+
+def _gpu_present():
+    import torch
+    return torch.cuda.device_count() > 0
+
+
+def test_denoise_validation_before_device_use():
+    """Every invalid argument is LRT_E_INVALID, a valid call without lrt_initialize() LRT_E_STATE:
+    no GPU needed for either, host and device entry points alike."""
+    lib = L.lib()
+    w, h = 16, 9
+    color = np.zeros((h, w, 4), np.float32)
+    out = np.zeros((h, w, 4), np.float32)
+    guide = np.zeros((h, w, 4), np.float32)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)   # noqa: E731
+
+    def desc(**kw):
+        d = L.DenoiseDesc()
+        assert lib.lrt_denoise_default(w, h, ctypes.byref(d)) == 0
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    def calls(d, c, g, o):
+        dp = ctypes.byref(d) if d is not None else None
+        gp = ctypes.byref(g) if g is not None else None
+        return (lib.lrt_denoise_host(dp, c, gp, o), lib.lrt_denoise_device(dp, c, gp, o, None))
+
+    inv = (L.LRT_E_INVALID, L.LRT_E_INVALID)
+    assert calls(None, ptr(color), None, ptr(out)) == inv
+    assert calls(desc(), None, None, ptr(out)) == inv
+    assert calls(desc(), ptr(color), None, None) == inv
+    for bad in (dict(width=0), dict(height=0), dict(width=-3), dict(iterations=0),
+                dict(iterations=L.DENOISE_MAX_ITER + 1), dict(iterations=-1), dict(flags=1)):
+        assert calls(desc(**bad), ptr(color), None, ptr(out)) == inv, bad
+    for name in ("sigma_color", "sigma_normal", "sigma_pos", "sigma_albedo"):
+        for v in (0.0, -1.0, float("inf"), float("nan")):
+            assert calls(desc(**{name: v}), ptr(color), None, ptr(out)) == inv, (name, v)
+    for name in L.GUIDE_NAMES:   # out may not be a guide buffer
+        g = L.Features()
+        setattr(g, name, guide.ctypes.data)
+        assert calls(desc(), ptr(color), g, ptr(guide)) == inv, name
+    assert "guide" in lib.lrt_last_error().decode()
+    if os.environ.get("HIP_VISIBLE_DEVICES") == "" or not _gpu_present():
+        g = L.Features()
+        g.normal = guide.ctypes.data
+        assert calls(desc(), ptr(color), g, ptr(out)) == (L.LRT_E_STATE, L.LRT_E_STATE)
+        assert calls(desc(), ptr(color), None, ptr(color)) == (L.LRT_E_STATE, L.LRT_E_STATE)   # in place is valid
+
+
+def test_denoise_default_desc():
+    lib = L.lib()
+    assert ctypes.sizeof(L.DenoiseDesc) == 32
+    d = L.DenoiseDesc()
+    assert lib.lrt_denoise_default(1280, 720, ctypes.byref(d)) == 0
+    assert (d.width, d.height, d.iterations, d.flags) == (1280, 720, 5, 0)
+    assert L.DENOISE_MAX_ITER == 5 == R.DEFAULTS["iterations"]
+    for name in ("sigma_color", "sigma_normal", "sigma_pos", "sigma_albedo"):
+        assert getattr(d, name) == np.float32(R.DEFAULTS[name]), name
+    assert (R.DEFAULTS["sigma_color"], R.DEFAULTS["sigma_normal"], R.DEFAULTS["sigma_pos"],
+            R.DEFAULTS["sigma_albedo"]) == (2.0, 0.3, 0.5, 0.2)
+    assert lib.lrt_denoise_default(1280, 720, None) == L.LRT_E_INVALID
+    assert lib.lrt_denoise_default(0, 720, ctypes.byref(d)) == L.LRT_E_INVALID
+
+
+def test_python_front_end_rejects_bad_arguments():
+    from learnraytracing_amd import LrtError, denoise_host
+    color = np.zeros((9, 16, 4), np.float32)
+    with pytest.raises(LrtError):
+        denoise_host(color, {"depth": color.copy()})
+    with pytest.raises(LrtError):
+        denoise_host(color, None, sigma=1.0)
+    with pytest.raises(LrtError):
+        denoise_host(color.ravel(), None)
+    with pytest.raises(LrtError):
+        denoise_host(color, {"normal": np.zeros((9, 16, 3), np.float32)})
+
+
+def test_filter_quality_on_reference_render():
+    """The specified filter earns its place: on the oracle's 160x90, 4 spp, depth 8 render with
+    features, the f64 restatement with the defaults brings the MSE against the 1024 spp render to
+    <= 0.5x and the relative MSE to <= 0.1x of the noisy frame's (measured: 0.35x, 0.040x)."""
+    w, h = 160, 90
+    feats = {n: np.zeros((h, w, 4), np.float32) for n in oracle.FEATURE_NAMES}
+    noisy, _ = oracle.orc_render_ex(w, h, frames=4, depth=8, features=feats, max_frame=4)
+    gt, _ = oracle.orc_render(w, h, frames=1024, depth=8)
+    guides = {n: feats[n] for n in L.GUIDE_NAMES}
+    got = R.atrous(noisy, guides, np.float64)
+    m0, m1 = R.mse(noisy, gt), R.mse(got, gt)
+    r0, r1 = R.rel_mse(noisy, gt), R.rel_mse(got, gt)
+    print(f"MSE {m0:.4g} -> {m1:.4g} ({m1 / m0:.3f}x), relMSE {r0:.4g} -> {r1:.4g} ({r1 / r0:.4f}x)")
+    assert m1 <= 0.5 * m0
+    assert r1 <= 0.1 * r0
+
+
+def test_restatement_constant_image_stays_constant():
+    color, guides = R.synthetic_inputs(37, 21)
+    color[..., :3] = np.float32([0.25, 1.5, 3.0])
+    for names in R.GUIDE_SETS.values():
+        got = R.atrous(color, {k: guides[k] for k in names}, np.float64)
+        assert np.abs(got - np.float64(color[..., :3])).max() <= 1e-12, names
+
+
+def test_restatement_orthogonal_half_planes_do_not_mix():
+    """Two half-planes with orthogonal normals, sigma_normal 0.1: |dn|^2 / sigma^2 = 200, the
+    cross weights are exp(-200) ~ 1e-87 -- zero against the same-side weights in f64 too -- so
+    each side's output is a mean of its own side only."""
+    w, h = 48, 20
+    color = np.zeros((h, w, 4), np.float32)
+    color[:, : w // 2, :3] = 1.0
+    color[:, w // 2:, :3] = 3.0
+    normal = np.zeros((h, w, 4), np.float32)
+    normal[:, : w // 2, 1] = 1.0
+    normal[:, w // 2:, 0] = 1.0
+    for dtype in (np.float32, np.float64):
+        got = R.atrous(color, {"normal": normal}, dtype, sigma_normal=0.1)
+        assert np.array_equal(got, color[..., :3].astype(dtype))
+    mixed = R.atrous(color, None, np.float64)   # and without the guide they do mix
+    assert 1.0 < mixed[h // 2, w // 2 - 1, 0] < 3.0
+
+
+def test_restatement_null_guides_drop_their_terms():
+    color, guides = R.synthetic_inputs(40, 24)
+    none = R.atrous(color, None, np.float64, iterations=3)
+    assert np.array_equal(none, R.atrous(color, {}, np.float64, iterations=3))
+    assert np.array_equal(none, R.atrous(color, {"normal": None, "color_std": None}, np.float64, iterations=3))
+    # an unguided pass is the plain B3-spline blur, renormalised at the border
+    one = R.atrous(color, None, np.float64, iterations=1)
+    c = np.float64(color[..., :3])
+    y, x = 12, 20
+    k = np.outer(R.H5, R.H5)
+    assert np.allclose(one[y, x], (k[..., None] * c[y - 2:y + 3, x - 2:x + 3]).sum((0, 1)), rtol=1e-13)
+    k00 = k[2:, 2:]
+    assert np.allclose(one[0, 0], (k00[..., None] * c[:3, :3]).sum((0, 1)) / k00.sum(), rtol=1e-13)
+    # each guide changes the result, and a term scales with its sigma only
+    for name in L.GUIDE_NAMES:
+        assert not np.array_equal(none, R.atrous(color, {name: guides[name]}, np.float64, iterations=3)), name
+    a = R.atrous(color, {"normal": guides["normal"]}, np.float64, sigma_pos=0.01, sigma_albedo=7.0, sigma_color=9.0)
+    assert np.array_equal(a, R.atrous(color, {"normal": guides["normal"]}, np.float64))
+
+
+def test_denoise_bench_byte_count():
+    """tools/denoise_bench.py's bytes per pass, from the tile geometry: a frame of exactly one tile
+    stages itself once; a large frame stages ~2.1x (s = 1) to ~4x (s = 16) its pixels; never less
+    than the compulsory 64 B per pixel."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("denoise_bench", os.path.join(root, "tools", "denoise_bench.py"))
+    B = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(B)
+    assert B.pass_bytes(64, 4, 1, False) == 64 * 4 * (64 + 16 + 16)
+    assert B.pass_bytes(64, 4, 1, True) == 64 * 4 * (64 + 16 + 12)
+    w, h = 1280, 720
+    for s, lo, hi in ((1, 2.0, 2.2), (16, 3.5, 4.0)):
+        staged = (B.pass_bytes(w, h, s, False) - w * h * 32) / 64 / (w * h)
+        assert lo <= staged <= hi, (s, staged)
+        assert B.pass_bytes(w, h, s, True) >= B.MIN_BYTES_PER_PIXEL * w * h
+    with pytest.raises(SystemExit):
+        B.main(["--reps", "5"])
