@@ -316,8 +316,8 @@ int lrt_present_bgra8(const float* d_rgba, uint32_t* d_bgra, int width, int heig
  *
  * Whole frames only: every buffer is height rows of width RGBA float quads. A
  * row-block-cyclic shard (row_period > 1) lacks its rows' neighbours and cannot be filtered
- * on its own -- assemble the frame first. No temporal reuse, no albedo demodulation, and the
- * variance guide itself is not filtered. */
+ * on its own -- assemble the frame first. No temporal reuse of its own (lrt_temporal_* below is
+ * the stage for that), no albedo demodulation, and the variance guide itself is not filtered. */
 #define LRT_DENOISE_MAX_ITER 5
 typedef struct lrt_denoise_desc {
     int32_t width, height;      /* a whole frame: height rows of width RGBA float quads */
@@ -343,6 +343,108 @@ int lrt_denoise_device(const lrt_denoise_desc* desc, const float* d_color, const
 /* Same on HOST buffers: staged through device memory, blocking; the output equals
  * lrt_denoise_device's bit for bit. */
 int lrt_denoise_host(const lrt_denoise_desc* desc, const float* color, const lrt_features* guides, float* out);
+
+/* ---- temporal reprojection and accumulation ------------------------------------ */
+
+/* The first stage of SVGF, ahead of the denoiser: find each pixel's surface point in the previous
+ * frame, blend that frame's history in, and keep a second moment, so that render (1-4 spp, moving
+ * camera) -> temporal accumulate -> denoise -> present stays on the device and the denoiser gets a
+ * variance guide that a single frame cannot give. All buffers are whole frames: `height` rows of
+ * `width` RGBA float quads, row 0 at the bottom. f32 throughout.
+ *
+ * Per pixel p = (x, y), with the current colour and guides each times cur_scale = k:
+ *     C = k color.rgb, N = k normal.rgb, X = k world_pos.rgb, A = k albedo.rgb
+ * the current camera O, L, H, V (origin, lowerLeftCorner, horizontalVec, verticalVec) and the
+ * previous camera O', a', L', H', V':
+ *  1. hit = |N|^2 >= 0.25 (a camera miss has zero features; a pixel whose samples mix hit and
+ *     miss counts as a miss below one half).
+ *  2. Pixel-centre direction D = L + ((x + 1/2) / w) H + ((y + 1/2) / h) V - O.
+ *  3. The surface point of the pixel CENTRE, not of the jittered sample (reprojecting the jittered
+ *     X lands up to half a pixel off and blurs the history even under a static camera): if hit,
+ *     |D.N| > 1e-3 |D| and lambda = ((X - O).N) / (D.N) > 0 then Xc = O + lambda D, else Xc = X.
+ *     The target is d = Xc - O' for a hit, d = D (the point at infinity that way) for a miss.
+ *  4. Into the previous camera: da = d.a' (in front iff da < 0), fd = -(L' - O').a',
+ *     q = (-fd / da) d - (L' - O'), fx = (q.H') / (H'.H') w - 1/2, fy = (q.V') / (V'.V') h - 1/2.
+ *     No history if the point is not in front, if anything is non-finite, or if |fx| or |fy| is
+ *     >= 1e6. The lens offset is ignored.
+ *  5. Four bilinear taps Q = (floor(fx) + i, floor(fy) + j), i, j in 0..1, weights b_ij. A tap
+ *     counts iff it lies inside the image and is consistent: with hit'(Q) = |N'(Q)|^2 >= 0.25, a
+ *     hit pixel needs hit'(Q), N'(Q).N >= normal_min and
+ *     |X'(Q) - Xc|^2 <= pos_tol^2 |Xc - O|^2; a miss pixel needs !hit'(Q).
+ *  6. sw = sum of b over the counting taps. With sw > 1e-3: history n = sum b n'(Q) / sw + 1,
+ *     alpha = max(1 / n, alpha_min), color = (1 - alpha) sum b c'(Q) / sw + alpha C,
+ *     moment2 = (1 - alpha) sum b m2'(Q) / sw + alpha C^2 per channel. Otherwise, and whenever
+ *     there is no previous state: color = C, moment2 = C^2, n = 1.
+ *  7. std = sqrt(max(moment2 - color^2, 0)) per channel; where n < min_history,
+ *     std = (short_std, short_std, short_std) instead: a large value switches the denoiser's colour
+ *     term off where the variance is not yet known (a disoccluded pixel would otherwise have
+ *     std = 0, which the denoiser reads as "keep").
+ * Outputs (the next state): color rgb (alpha untouched); moment2 rgb with n in its alpha;
+ * normal = N, world_pos = X (the scaled inputs, alpha written as 0: the next step's history
+ * guides and ready-made denoiser guides); albedo = A when both the input and the output are
+ * given; color_std rgb (alpha untouched) if requested, in the layout lrt_denoise_device reads.
+ *
+ * cur_scale exists because lrt_render_desc.frame0 couples the seed to the lerp weight: a render
+ * of samples frame0 .. frame0 + frames - 1 into ZEROED buffers with max_frame < 0 leaves
+ * sum / (frame0 + frames); k = (frame0 + frames) / frames turns that into the plain mean of the
+ * fresh samples. That is how a caller gets new seeds every time step without touching the render
+ * kernels (a static camera re-rendering frame0 = 0 would accumulate identical frames).
+ *
+ * Limits: whole frames only. Static scene: the camera moves, the spheres do not. First-hit
+ * reprojection only: reflections and refractions lag. Like the denoiser it is not bit-pinned (the
+ * reference has no such stage) but tolerance-checked against its NumPy restatement
+ * (tests/temporal_ref.py); it is deterministic run to run. */
+typedef struct lrt_temporal_desc {
+    int32_t width, height;      /* a whole frame */
+    int32_t flags;              /* 0 */
+    int32_t min_history;        /* >= 1 */
+    lrt_camera camera, prev_camera;
+    float cur_scale;            /* finite, > 0 */
+    float alpha_min;            /* in (0, 1] */
+    float normal_min;           /* in [-1, 1] */
+    float pos_tol, short_std;   /* finite, > 0 */
+    int32_t reserved;           /* 0 */
+} lrt_temporal_desc;
+
+/* One accumulation state: five frames (albedo may be NULL). */
+typedef struct lrt_temporal_state {
+    float* color;
+    float* moment2;   /* rgb: the running second moment; alpha: the history length n */
+    float* normal;
+    float* world_pos;
+    float* albedo;
+} lrt_temporal_state;
+
+/* The defaults for a width x height frame and a camera pair: alpha_min 0.05, normal_min 0.9,
+ * pos_tol 0.05, min_history 4, short_std 1e3, cur_scale 1. prev_camera == NULL: the camera. */
+int lrt_temporal_default(int width, int height, const lrt_camera* camera, const lrt_camera* prev_camera,
+                         lrt_temporal_desc* out);
+
+/* One step on device buffers. d_color: the current frame's colour. d_cur: its normal and
+ * world_pos (required) and albedo (optional); the other members are ignored. d_prev: the previous
+ * state, or NULL for no history (everything is reset); if given, its color, moment2, normal and
+ * world_pos are required. d_next: the state written; the same four are required, albedo is
+ * optional. d_color_std may be NULL.
+ *
+ * No aliasing: the kernel gathers from d_prev at arbitrary pixels, so the step cannot run in place
+ * and the caller ping-pongs two states. No d_next buffer and no d_color_std may overlap a d_prev
+ * buffer, an input, or each other (LRT_E_INVALID).
+ *
+ * LRT_E_INVALID, before any device use: NULL required pointers; sizes < 1 or
+ * width * height > INT_MAX / 4; flags or reserved != 0; min_history < 1; non-finite parameters;
+ * cur_scale, pos_tol or short_std <= 0; alpha_min outside (0, 1]; normal_min outside [-1, 1]; a
+ * prev_camera whose H'.H', V'.V' or fd is not finite and > 0. Asynchronous on `stream` and ordered
+ * only against it, like lrt_render_device. Acts on the first device. */
+int lrt_temporal_accumulate_device(const lrt_temporal_desc* desc, const float* d_color, const lrt_features* d_cur,
+                                   const lrt_temporal_state* d_prev, const lrt_temporal_state* d_next,
+                                   float* d_color_std, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_temporal_accumulate_device's bit for bit (the alphas of next->color and color_std are the
+ * host buffers' own). */
+int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* color, const lrt_features* cur,
+                                 const lrt_temporal_state* prev, const lrt_temporal_state* next,
+                                 float* color_std);
 
 #ifdef __cplusplus
 }

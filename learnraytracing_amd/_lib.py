@@ -102,6 +102,23 @@ class DenoiseDesc(ctypes.Structure):          # lrt_denoise_desc
                 ("sigma_pos", ctypes.c_float), ("sigma_albedo", ctypes.c_float)]
 
 
+class TemporalDesc(ctypes.Structure):         # lrt_temporal_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("min_history", ctypes.c_int32),
+                ("camera", Camera), ("prev_camera", Camera),
+                ("cur_scale", ctypes.c_float), ("alpha_min", ctypes.c_float), ("normal_min", ctypes.c_float),
+                ("pos_tol", ctypes.c_float), ("short_std", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+class TemporalState(ctypes.Structure):        # lrt_temporal_state
+    _fields_ = [("color", ctypes.c_void_p), ("moment2", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("world_pos", ctypes.c_void_p), ("albedo", ctypes.c_void_p)]
+
+
+TEMPORAL_STATE_NAMES = ("color", "moment2", "normal", "world_pos", "albedo")
+TEMPORAL_CUR_NAMES = ("normal", "world_pos", "albedo")   # what lrt_temporal_* reads of lrt_features
+TEMPORAL_PARAMS = ("cur_scale", "alpha_min", "normal_min", "pos_tol", "short_std", "min_history")
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -143,6 +160,11 @@ SIGNATURES = {
     "lrt_denoise_default": (_i, [_i, _i, _c.POINTER(DenoiseDesc)]),
     "lrt_denoise_device": (_i, [_c.POINTER(DenoiseDesc), _vp, _c.POINTER(Features), _vp, _vp]),
     "lrt_denoise_host": (_i, [_c.POINTER(DenoiseDesc), _vp, _c.POINTER(Features), _vp]),
+    "lrt_temporal_default": (_i, [_i, _i, _c.POINTER(Camera), _c.POINTER(Camera), _c.POINTER(TemporalDesc)]),
+    "lrt_temporal_accumulate_device": (_i, [_c.POINTER(TemporalDesc), _vp, _c.POINTER(Features),
+                                            _c.POINTER(TemporalState), _c.POINTER(TemporalState), _vp, _vp]),
+    "lrt_temporal_accumulate_host": (_i, [_c.POINTER(TemporalDesc), _vp, _c.POINTER(Features),
+                                          _c.POINTER(TemporalState), _c.POINTER(TemporalState), _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

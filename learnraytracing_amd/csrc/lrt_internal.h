@@ -10,6 +10,7 @@
 //   lrt_multi.hip     one process, several devices: split, RCCL gather, IPC frames
 //   lrt_frame.hip     frame assembly and present kernels
 //   lrt_denoise.hip   the feature-guided a-trous denoiser (lrt_denoise_*): kernel and entry points
+//   lrt_temporal.hip  temporal reprojection and accumulation (lrt_temporal_*): kernel and entry points
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
 #pragma once
@@ -37,7 +38,7 @@
 #include "lrt_diag.h"
 #include "lrt_trace.h"
 
-#define LRT_VERSION_STRING "lrt-mi355x 0.3.0 gfx950"
+#define LRT_VERSION_STRING "lrt-mi355x 0.4.0 gfx950"
 
 namespace lrt {
 

@@ -382,6 +382,166 @@ def denoise_tensor(color, guides: Optional[dict], out=None, stream=None, **param
     return out
 
 
+# ---- temporal reprojection and accumulation ------------------------------------------------
+def temporal_desc(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera] = None,
+                  **params) -> L.TemporalDesc:
+    """lrt_temporal_default for a width x height frame seen from `camera`, the previous frame from
+    `prev_camera` (None: the same camera), with any of cur_scale, alpha_min, normal_min, pos_tol,
+    short_std, min_history overridden."""
+    if not isinstance(camera, L.Camera) or not (prev_camera is None or isinstance(prev_camera, L.Camera)):
+        raise L.LrtError(L.LRT_E_INVALID, "camera and prev_camera must be Camera structs")
+    d = L.TemporalDesc()
+    L.check(L.lib().lrt_temporal_default(int(width), int(height), ctypes.byref(camera),
+                                         ctypes.byref(prev_camera) if prev_camera is not None else None,
+                                         ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.TEMPORAL_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown temporal parameter {name!r}")
+        setattr(d, name, int(v) if name == "min_history" else float(v))
+    return d
+
+
+def _temporal_call(entry, color, cur, prev, out, n, check, ptr, make, extra):
+    """The argument marshalling the host and tensor front ends share: check(buf, what) validates a
+    buffer of >= n elements, ptr(buf) is its address, make() a zeroed frame. Returns the new state."""
+    check(color, "color")
+    if not isinstance(cur, dict) or "normal" not in cur or "world_pos" not in cur:
+        raise L.LrtError(L.LRT_E_INVALID, "cur must hold normal and world_pos")
+    f = L.Features()
+    for name, buf in cur.items():
+        if name not in L.TEMPORAL_CUR_NAMES:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown feature {name!r}")
+        check(buf, name)
+        setattr(f, name, ptr(buf))
+    ps = None
+    if prev is not None:
+        ps = L.TemporalState()
+        for name in L.TEMPORAL_STATE_NAMES[:4]:
+            if name not in prev:
+                raise L.LrtError(L.LRT_E_INVALID, f"prev lacks {name!r}")
+        for name, buf in prev.items():
+            if name == "color_std":      # a returned state may be passed back as it is
+                continue
+            if name not in L.TEMPORAL_STATE_NAMES:
+                raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
+            check(buf, "prev " + name)
+            setattr(ps, name, ptr(buf))
+    if out is None:
+        out = {name: make() for name in L.TEMPORAL_STATE_NAMES[:4] + ("color_std",)}
+        if "albedo" in cur:
+            out["albedo"] = make()
+    ns = L.TemporalState()
+    std = None
+    for name in L.TEMPORAL_STATE_NAMES[:4]:
+        if name not in out:
+            raise L.LrtError(L.LRT_E_INVALID, f"out lacks {name!r}")
+    for name, buf in out.items():
+        if name not in L.TEMPORAL_STATE_NAMES + ("color_std",):
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
+        check(buf, "out " + name)
+        if name == "color_std":
+            std = ptr(buf)
+        else:
+            setattr(ns, name, ptr(buf))
+    L.check(entry(ctypes.c_void_p(ptr(color)), ctypes.byref(f), ctypes.byref(ps) if ps is not None else None,
+                  ctypes.byref(ns), ctypes.c_void_p(std) if std else None, *extra))
+    return out
+
+
+def temporal_accumulate_host(color: np.ndarray, cur: dict, prev: Optional[dict], camera: L.Camera,
+                             prev_camera: Optional[L.Camera] = None, out: Optional[dict] = None, **params) -> dict:
+    """One temporal accumulation step on host buffers (lrt_temporal_accumulate_host). color: the
+    current frame, float32 [height, width, 4] (or flat with width=, height=); cur: its features
+    {"normal", "world_pos"[, "albedo"]} as render_host_features fills them; prev: the state a
+    previous call returned, or None for no history; camera / prev_camera: this frame's and the
+    previous frame's camera. out: the destination buffers {"color", "moment2", "normal",
+    "world_pos"[, "albedo"][, "color_std"]} (none may be an input or a prev buffer; the alphas of
+    color and color_std stay), default new zeroed ones. params: cur_scale, alpha_min, normal_min,
+    pos_tol, short_std, min_history. Returns the new state (out), color_std included."""
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = temporal_desc(w, h, camera, prev_camera, **params)
+    n = w * h * 4
+
+    def check(buf, what):
+        _check_host_buffer(buf, n)
+
+    return _temporal_call(lambda *a: L.lib().lrt_temporal_accumulate_host(ctypes.byref(d), *a), color, cur, prev,
+                          out, n, check, lambda b: b.ctypes.data, lambda: np.zeros((h, w, 4), np.float32), ())
+
+
+def temporal_accumulate_tensor(color, cur: dict, prev: Optional[dict], camera: L.Camera,
+                               prev_camera: Optional[L.Camera] = None, out: Optional[dict] = None, stream=None,
+                               **params) -> dict:
+    """temporal_accumulate_host on cuda float32 tensors (lrt_temporal_accumulate_device):
+    asynchronous on `stream` (a torch.cuda.Stream, default: current) and ordered only against it.
+    Returns the new state."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = temporal_desc(w, h, camera, prev_camera, **params)
+    n = w * h * 4
+    if not getattr(color, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color.device)
+
+    def check(t, what):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == torch.float32
+                and t.is_contiguous() and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda float32 tensor of >= {n} elements")
+
+    def make():
+        with torch.cuda.stream(s):
+            return torch.zeros((h, w, 4), device=color.device)
+
+    return _temporal_call(lambda *a: L.lib().lrt_temporal_accumulate_device(ctypes.byref(d), *a), color, cur, prev,
+                          out, n, check, lambda t: t.data_ptr(), make, (ctypes.c_void_p(s.cuda_stream),))
+
+
+class TemporalAccumulator:
+    """The two ping-pong states of a width x height frame on `device` and the previous camera:
+    step() blends a freshly rendered frame into the history and returns what the denoiser takes."""
+
+    def __init__(self, width: int, height: int, device="cuda:0"):
+        import torch
+
+        self.width, self.height = int(width), int(height)
+        if self.width < 1 or self.height < 1:
+            raise L.LrtError(L.LRT_E_INVALID, "invalid image size")
+        self.device = torch.device(device)
+        names = L.TEMPORAL_STATE_NAMES + ("color_std",)
+        self._states = [{n: torch.zeros((self.height, self.width, 4), device=self.device) for n in names}
+                        for _ in range(2)]
+        self._cur = 0            # the state the last step wrote
+        self._camera = None      # its camera (None: no history)
+
+    def reset(self) -> None:
+        """Drop the history: the next step starts over (a new scene, a camera cut)."""
+        self._camera = None
+
+    def step(self, color, features: dict, camera: L.Camera, cur_scale: float = 1.0, stream=None, **params):
+        """One accumulation step (temporal_accumulate_tensor) of the frame `color` with its
+        features {"normal", "world_pos"[, "albedo"]} seen from `camera`. Returns (color, guides):
+        the accumulated frame and the dict denoise_tensor takes ("normal", "world_pos", "albedo"
+        if given, "color_std"); both are the accumulator's own tensors, valid until the step after
+        the next."""
+        cur = {k: v for k, v in features.items() if k in L.TEMPORAL_CUR_NAMES}
+        unknown = [k for k in features if k not in L.FEATURE_NAMES]
+        if unknown:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown feature {unknown[0]!r}")
+        nxt = self._states[1 - self._cur]
+        out = {k: v for k, v in nxt.items() if k != "albedo" or "albedo" in cur}
+        prev = None
+        if self._camera is not None:
+            prev = {k: v for k, v in self._states[self._cur].items() if k != "color_std"}
+        temporal_accumulate_tensor(color, cur, prev, camera, self._camera, out=out, stream=stream,
+                                   width=self.width, height=self.height, cur_scale=cur_scale, **params)
+        self._cur = 1 - self._cur
+        self._camera = L.Camera.from_buffer_copy(camera)
+        return nxt["color"], {k: nxt[k] for k in L.GUIDE_NAMES if k in out}
+
+
 def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
     """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
     import torch
