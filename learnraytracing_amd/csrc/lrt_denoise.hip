@@ -40,6 +40,12 @@ inline size_t tile_bytes(int s) { return sizeof(float2) * kPlanes * kTileLds * (
 // The taps are branch-free: pixels outside the image and absent guides are staged as zeros and
 // an out-of-image tap gets a zero spline weight; the guides are staged divided by their sigma
 // (times sqrt(log2 e), so that a tap's weight is one v_exp_f32 of its summed squares).
+// world_pos is staged relative to an anchor, the position at the workgroup's first pixel, as
+// fma(x, k, -(anchor k)): one rounding, of a value of the size of the tile's extent instead of
+// the scene's distance from the origin (x k alone: at 1000 units, sigma_pos 0.5, an ulp of the
+// staged value is 4e-4 of a sigma and the weights were off by 5e-5 of the result). The taps take
+// differences of staged values, in which the constant cancels, its own rounding included; a
+// non-finite component of the anchor counts as 0. No instruction more per staged pixel.
 // kStd: color_std is given (else there is no colour term).
 template <bool kStd>
 __global__ __launch_bounds__(kTileW* kTileRows) void denoise_kernel(DenoiseArgs a) {
@@ -52,6 +58,9 @@ __global__ __launch_bounds__(kTileW* kTileRows) void denoise_kernel(DenoiseArgs 
     const int y0 = (blockIdx.y / s) * (kTileRows * s) + blockIdx.y % s;
     if (y0 >= a.h) return;   // the whole workgroup: the last group's unused phases
     const float kn = a.kn, kx = a.kx, ka = a.ka;
+    const float4 an = a.pos[(size_t)y0 * a.w + x0];   // uniform over the workgroup, inside the image
+    auto finite_or_0 = [](const float v) { return fabsf(v) < INFINITY ? v : 0.0f; };   // (a NaN fails the compare)
+    const float ax = finite_or_0(-an.x * kx), ay = finite_or_0(-an.y * kx), az = finite_or_0(-an.z * kx);   // -(anchor k)
     // the centre's std first: its latency passes behind the staging
     const int px = x0 + tx, py = y0 + ty * s;
     const bool live = px < a.w && py < a.h;
@@ -87,8 +96,8 @@ __global__ __launch_bounds__(kTileW* kTileRows) void denoise_kernel(DenoiseArgs 
         t[0 * plane] = make_float2(ok[u] ? cc.x : 0.0f, ok[u] ? cc.y : 0.0f);
         t[1 * plane] = make_float2(ok[u] ? cc.z : 0.0f, on ? nn.x * kn : 0.0f);
         t[2 * plane] = make_float2(on ? nn.y * kn : 0.0f, on ? nn.z * kn : 0.0f);
-        t[3 * plane] = make_float2(ox ? xx.x * kx : 0.0f, ox ? xx.y * kx : 0.0f);
-        t[4 * plane] = make_float2(ox ? xx.z * kx : 0.0f, oa ? aa.x * ka : 0.0f);
+        t[3 * plane] = make_float2(ox ? fmaf(xx.x, kx, ax) : 0.0f, ox ? fmaf(xx.y, kx, ay) : 0.0f);
+        t[4 * plane] = make_float2(ox ? fmaf(xx.z, kx, az) : 0.0f, oa ? aa.x * ka : 0.0f);
         t[5 * plane] = make_float2(oa ? aa.y * ka : 0.0f, oa ? aa.z * ka : 0.0f);
     }
     float inv_c = 0.0f;

@@ -8,8 +8,9 @@ a conftest: imported by tests/test_denoise_cpu.py and tests/test_gpu_denoise.py.
       + |n(p) - n(q)|^2 / sigma_normal^2 + |x(p) - x(q)|^2 / sigma_pos^2 + |a(p) - a(q)|^2 / sigma_albedo^2
         (each only if its guide is given)
 
-`python tests/denoise_ref.py` prints the largest gap between the f32 and the f64 run over the GPU
-test's cases (the constant F32_F64_GAP of tests/test_gpu_denoise.py).
+`python tests/denoise_ref.py` prints the largest gap between the f32 and the f64 run over each of the
+GPU tests' two case tables (the constants F32_F64_GAP and F32_F64_GAP_EDGE of
+tests/test_gpu_denoise.py).
 """
 import numpy as np
 
@@ -79,11 +80,42 @@ GUIDE_SETS = {
 PALETTE = np.array([[0.8, 0.8, 0.8], [0.8, 0.4, 0.4], [0.4, 0.8, 0.4], [0.7, 0.7, 0.9]], np.float32)
 
 
-def synthetic_inputs(w, h, seed=0):
+VARIANTS = ("std_extremes", "fireflies", "dirty_alpha", "far_origin")
+FAR_ORIGIN = (1000.0, 0.0, 1000.0)
+
+
+def synthetic_inputs(w, h, seed=0, variant=None):
     """(color, guides): float32 [h, w, 4] buffers. colour: a smooth field plus noise in [0, 4];
     std in [0.05, 1]; normals: three plane regions plus jitter; position: a ramp plus jitter;
     albedo: a four-colour palette in blocks. The jitters are of the size of the default sigmas,
-    so that a fair share of the weights is neither 0 nor 1."""
+    so that a fair share of the weights is neither 0 nor 1.
+    variant (one of VARIANTS) changes the default frame afterwards, from a generator of its own:
+      std_extremes  color_std rgb exactly 0 on a third of the pixels, exactly 1e3 (the temporal
+                    stage's short_std) on another third
+      fireflies     up to five pixels at 1e4 and one at 65504
+      dirty_alpha   NaN, +Inf and 1e30 in the alpha of every guide buffer
+      far_origin    world_pos rgb shifted by FAR_ORIGIN, in f32"""
+    if variant is not None:
+        if variant not in VARIANTS:
+            raise ValueError(f"unknown variant {variant!r}")
+        color, guides = synthetic_inputs(w, h, seed)
+        rng = np.random.default_rng([VARIANTS.index(variant), w, h, seed])
+        if variant == "std_extremes":
+            third = rng.integers(0, 3, (h, w))
+            guides["color_std"][..., :3][third == 0] = 0.0
+            guides["color_std"][..., :3][third == 1] = 1e3
+        elif variant == "fireflies":
+            at = rng.choice(w * h, min(6, w * h), replace=False)
+            rgb = color.reshape(-1, 4)[:, :3]
+            rgb[at] = 1e4
+            rgb[at[-1]] = 65504.0
+        elif variant == "dirty_alpha":
+            junk = np.float32([np.nan, np.inf, 1e30])
+            for g in guides.values():
+                g[..., 3] = junk[rng.integers(0, 3, (h, w))]
+        else:
+            guides["world_pos"][..., :3] += np.float32(FAR_ORIGIN)
+        return color, guides
     rng = np.random.default_rng(1000 * w + h + seed)
     y, x = np.mgrid[0:h, 0:w].astype(np.float32)
     u, v = x / max(w - 1, 1), y / max(h - 1, 1)
@@ -118,17 +150,82 @@ def rel_gap(a, ref):
     return float((np.abs(np.asarray(a, np.float64) - ref) / np.maximum(1.0, np.abs(ref))).max())
 
 
-def f32_f64_gap():
+def case(w, h, iterations=5, guides=None, variant=None, **params):
+    """One filter call of a case table: synthetic_inputs(w, h, variant=variant), the guides named
+    (default: all four), atrous' parameters."""
+    return dict(w=w, h=h, variant=variant, guides=tuple(GUIDE_SETS["all"] if guides is None else guides),
+                params=dict(params, iterations=iterations))
+
+
+def case_label(c):
+    extra = "".join(f" {k}={v:g}" for k, v in c["params"].items() if k != "iterations")
+    return (f"{c['w']}x{c['h']} iterations={c['params']['iterations']} guides={'+'.join(c['guides']) or 'none'}"
+            f"{extra}{' ' + c['variant'] if c['variant'] else ''}")
+
+
+def case_inputs(c):
+    """(color, the case's guides) of one case."""
+    color, guides = synthetic_inputs(c["w"], c["h"], variant=c["variant"])
+    return color, {k: guides[k] for k in c["guides"]}
+
+
+def default_table():
+    """The cases of test_denoise_vs_restatement: SHAPES x ITERATIONS x GUIDE_SETS."""
+    return [case(w, h, it, names) for w, h in SHAPES for it in ITERATIONS for names in GUIDE_SETS.values()]
+
+
+# ---- the edge cases of tests/test_gpu_denoise.py::test_denoise_edges_vs_restatement: a base case
+# (67x45, 5 iterations, all guides, the default sigmas) and sweeps of one axis each from it, not
+# their product. At s = 16 a row group is 64 rows and a tile 64 columns: the shapes sit on and
+# beside those edges (one group exactly, a second group with one live phase, three groups, tall and
+# narrow) and run at the iteration counts that end on s = 4, 8 and 16, the three ping-pong parities.
+EDGE_BASE = (67, 45)
+EDGE_SHAPES = ((1, 130), (3, 70), (63, 5), (64, 4), (65, 8), (128, 3), (129, 65), (70, 129), (64, 64))
+EDGE_SHAPE_ITERATIONS = (3, 4, 5)
+# One frame of more workgroups than the device holds at once (256 x 16 of them at s = 8; about a
+# thousand are resident), the second row group's 2048 launches after the first's rows: a pass that
+# read the buffer it writes would pass every small frame, whose workgroups all stage before any
+# stores, and shows here. Unguided, so that the restatement of its 655 K pixels takes seconds.
+EDGE_WIDE = (16384, 40)
+EDGE_ITERATIONS = (1, 2, 3, 4, 5)
+EDGE_ITERATION_SHAPES = (EDGE_BASE, (129, 65))
+_ALL = GUIDE_SETS["all"]
+EDGE_GUIDE_SETS = {**{g: (g,) for g in _ALL}, **{"no_" + g: tuple(n for n in _ALL if n != g) for g in _ALL}}
+SIGMAS = ("sigma_color", "sigma_normal", "sigma_pos", "sigma_albedo")
+EDGE_SIGMA_FACTORS = (0.5, 3.0)
+EDGE_SIGMAS_ALL = dict(sigma_color=0.7, sigma_normal=2.5, sigma_pos=0.4, sigma_albedo=1.6)   # factors, all differ
+
+
+def edge_sweeps():
+    """{sweep: [case]}: the edge table, one entry per id of test_denoise_edges_vs_restatement."""
+    sweeps = {f"shape_{w}x{h}": [case(w, h, it) for it in EDGE_SHAPE_ITERATIONS] for w, h in EDGE_SHAPES}
+    sweeps["iterations"] = [case(w, h, it) for w, h in EDGE_ITERATION_SHAPES for it in EDGE_ITERATIONS]
+    sweeps["guides"] = [case(*EDGE_BASE, guides=names) for names in EDGE_GUIDE_SETS.values()]
+    sweeps["sigmas"] = [case(*EDGE_BASE, **{name: DEFAULTS[name] * f}) for name in SIGMAS for f in EDGE_SIGMA_FACTORS]
+    sweeps["sigmas"].append(case(*EDGE_BASE, **{name: DEFAULTS[name] * f for name, f in EDGE_SIGMAS_ALL.items()}))
+    sweeps["variants"] = [case(*EDGE_BASE, variant=v) for v in VARIANTS]
+    sweeps["wide"] = [case(*EDGE_WIDE, guides=())]
+    return sweeps
+
+
+def edge_table():
+    return [c for cases in edge_sweeps().values() for c in cases]
+
+
+def f32_f64_gap(table=None):
+    """The largest gap between the restatement's f32 and f64 runs over a case table (default: the
+    one of test_denoise_vs_restatement)."""
     worst = 0.0
-    for w, h in SHAPES:
-        color, guides = synthetic_inputs(w, h)
-        for it in ITERATIONS:
-            for names in GUIDE_SETS.values():
-                g = {k: guides[k] for k in names}
-                worst = max(worst, rel_gap(atrous(color, g, np.float32, iterations=it),
-                                           atrous(color, g, np.float64, iterations=it)))
+    for c in default_table() if table is None else table:
+        color, g = case_inputs(c)
+        worst = max(worst, rel_gap(atrous(color, g, np.float32, **c["params"]),
+                                   atrous(color, g, np.float64, **c["params"])))
     return worst
 
 
 if __name__ == "__main__":
     print(f"largest f32 - f64 gap over the GPU test's cases: {f32_f64_gap():.3g}")
+    print(f"largest f32 - f64 gap over the edge table ({len(edge_table())} filter calls): "
+          f"{f32_f64_gap(edge_table()):.3g}")
+    for name, cases in edge_sweeps().items():
+        print(f"  {name}: {f32_f64_gap(cases):.3g}")

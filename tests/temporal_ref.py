@@ -21,7 +21,8 @@ camera O, L, H, V and the previous camera O', a', L', H', V':
 
 `python tests/temporal_ref.py` prints the largest gap between the f32 and the f64 run over the GPU
 test's cases (the constants F32_F64_GAP and F32_F64_GAP_STD of tests/test_gpu_temporal.py) and the
-share of fragile pixels per case.
+share of fragile pixels per case, then the same over the designed cases (F32_F64_GAP_DESIGNED and
+F32_F64_GAP_STD_DESIGNED).
 """
 import numpy as np
 
@@ -47,12 +48,25 @@ def _near(v, thr):
     return np.abs(v - thr) <= FRAGILE_REL * np.maximum(np.abs(thr), np.abs(v))
 
 
-def step(color, cur, prev, camera, prev_camera, dtype=np.float64, **params):
+INFO_MASKS = ("hit", "centred", "grazing", "lam_le0", "ok", "keep", "alpha_clamped", "short_history",
+              "var_clamped")
+INFO_COUNTS = ("taps_inside", "rej_normal", "rej_pos", "rej_hitmiss")
+
+
+def step(color, cur, prev, camera, prev_camera, dtype=np.float64, info=None, **params):
     """One step. color [h, w, >= 3]; cur {"normal", "world_pos"[, "albedo"]}; prev: a state
     {"color", "moment2" (n in its alpha), "normal", "world_pos"} of [h, w, 4] buffers, or None.
     Arithmetic in `dtype`. Returns (state, fragile): state maps OUTPUTS to [h, w, 3] arrays ("n":
     [h, w]; "albedo" only if cur has it) in `dtype`; fragile [h, w] marks the pixels one of whose
-    decisions lies within FRAGILE_REL of its threshold."""
+    decisions lies within FRAGILE_REL of its threshold.
+    info: a dict to fill with the per-pixel decisions, [h, w] each (the return is the same with it):
+      INFO_MASKS   hit; centred (step 3 took the pixel centre's point); grazing (a hit with |D.N| <=
+                   1e-3 |D|); lam_le0 (a hit, not grazing, with lambda <= 0); ok (step 4: projectable);
+                   keep (step 6 blended the history in); alpha_clamped (alpha_min > 1 / n there);
+                   short_history (n < min_history); var_clamped (moment2 - color^2 < 0 in a channel)
+      INFO_COUNTS  taps_inside (0..4 in the image); of those, rej_normal (hit onto hit, the normal
+                   alone fails), rej_pos (hit onto hit, the position alone fails), rej_hitmiss (a
+                   hit onto a miss or a miss onto a hit)"""
     p = dict(DEFAULTS, **params)
     T = dtype
     k = T(p["cur_scale"])
@@ -65,6 +79,9 @@ def step(color, cur, prev, camera, prev_camera, dtype=np.float64, **params):
         out["albedo"] = k * np.asarray(cur["albedo"])[..., :3].astype(T)
     fragile = np.zeros((h, w), bool)
     col, m2, n = C.copy(), C * C, np.ones((h, w), T)
+    if info is not None:
+        info.update({name: np.zeros((h, w), bool) for name in INFO_MASKS})
+        info.update({name: np.zeros((h, w), np.int64) for name in INFO_COUNTS})
     if prev is not None:
         cam, pcm = _cam(camera, T), _cam(prev_camera, T)
         O, pO, pa = cam["O"], pcm["O"], pcm["a"]
@@ -117,6 +134,12 @@ def step(color, cur, prev, camera, prev_camera, dtype=np.float64, **params):
                 fragile |= inside & (_near(npn, T(0.25)) |
                                      (hit & hitp & (_near(ndot, T(p["normal_min"])) | _near(dist, lim))))
                 bw = np.where(inside & same, b, T(0))
+                if info is not None:
+                    nok, xok = ndot >= T(p["normal_min"]), dist <= lim
+                    info["taps_inside"] += inside
+                    info["rej_normal"] += inside & hit & hitp & ~nok & xok
+                    info["rej_pos"] += inside & hit & hitp & nok & ~xok
+                    info["rej_hitmiss"] += inside & (hit != hitp)
                 sw += bw
                 sn += bw * pm[cy, cx, 3]
                 sc += bw[..., None] * pc[cy, cx]
@@ -130,9 +153,15 @@ def step(color, cur, prev, camera, prev_camera, dtype=np.float64, **params):
             col = np.where(keep[..., None], (T(1) - al) * (sc / swc) + al * C, C)
             m2 = np.where(keep[..., None], (T(1) - al) * (sm / swc) + al * (C * C), C * C)
             n = np.where(keep, nh, T(1))
+        if info is not None:
+            grazing = hit & ~(np.abs(dn) > dlen)
+            info.update(hit=hit, centred=centred, grazing=grazing, lam_le0=hit & ~grazing & ~(lam > 0), ok=ok,
+                        keep=keep, alpha_clamped=keep & (T(p["alpha_min"]) > T(1) / nh))
     fragile |= _near(n, T(p["min_history"]))
     std = np.sqrt(np.maximum(m2 - col * col, T(0)))
     std = np.where((n < T(p["min_history"]))[..., None], T(p["short_std"]), std)
+    if info is not None:
+        info.update(short_history=n < T(p["min_history"]), var_clamped=(m2 - col * col < 0).any(-1))
     out.update(color=col, moment2=m2, n=n, color_std=std)
     return out, fragile
 
@@ -246,6 +275,155 @@ def f32_f64_gap(render, make_camera):
     return worst, worst_std, shares
 
 
+# ---- the designed scenes of tests/test_gpu_temporal.py::test_step_designed_cases: planes seen from
+# cameras placed so that each branch of the step holds pixels by construction (the rendered orbit
+# reaches few of them); tests/test_temporal_cpu.py::test_designed_cases_cover_their_branches counts.
+JITTER = 0.3
+
+
+def plane_frame(w, h, camera, planes, seed):
+    """(color, features, hit) of up to three planes seen from a 22-float camera through its origin
+    (a pinhole), in pure NumPy: one ray per pixel through (x + 1/2 + jx, y + 1/2 + jy), jx, jy
+    uniform in +-JITTER px; the nearest hit wins. A plane is dict(p=point, n=unit normal[, lo=, hi=:
+    the box its hits lie in]). color: random in [0.05, 2]; features: float32 [h, w, 4] "normal"
+    (the plane's, turned against the ray), "world_pos" and "albedo", all 0 on a miss."""
+    assert 1 <= len(planes) <= 3
+    rng = np.random.default_rng(seed)
+    c = cam22(camera).astype(np.float64)
+    O, L, H, V = c[0:3], c[12:15], c[15:18], c[18:21]
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    u = (xs + 0.5 + rng.uniform(-JITTER, JITTER, (h, w))) / w
+    v = (ys + 0.5 + rng.uniform(-JITTER, JITTER, (h, w))) / h
+    D = L + u[..., None] * H + v[..., None] * V - O
+    best = np.full((h, w), np.inf)
+    X, N, A = np.zeros((h, w, 3)), np.zeros((h, w, 3)), np.zeros((h, w, 3))
+    for i, pl in enumerate(planes):
+        P, n = np.float64(pl["p"]), np.float64(pl["n"])
+        dn = D @ n
+        with np.errstate(all="ignore"):
+            t = ((P - O) @ n) / dn
+        Xi = O + t[..., None] * D
+        good = np.isfinite(t) & (t > 0) & (t < best)
+        if "lo" in pl:
+            good &= (Xi >= np.float64(pl["lo"])).all(-1) & (Xi <= np.float64(pl["hi"])).all(-1)
+        best = np.where(good, t, best)
+        X[good] = Xi[good]
+        N[good] = (n * -np.sign(dn)[..., None])[good]
+        A[good] = (0.3 + 0.2 * i, 0.5, 0.7 - 0.2 * i)
+    color = np.zeros((h, w, 4), np.float32)
+    color[..., :3] = rng.uniform(0.05, 2.0, (h, w, 3))
+    feats = {}
+    for name, a in (("normal", N), ("world_pos", X), ("albedo", A)):
+        feats[name] = np.zeros((h, w, 4), np.float32)
+        feats[name][..., :3] = a
+    return color, feats, np.isfinite(best)
+
+
+def make_prev(guides, seed, n_range=(1.0, 20.0), under_moment=False):
+    """random_prev with n drawn from n_range (log-uniformly: short histories are as frequent as
+    long ones, and survive the blending of four taps) and, if under_moment, moment2 rgb = 0.5 x color^2 (less
+    than any variance allows) on a tenth of the pixels, in 4 x 4 blocks so that all four taps of
+    a reprojection can fall into one."""
+    st = random_prev(guides, seed)
+    h, w = st["color"].shape[:2]
+    st["moment2"][..., 3] = np.random.default_rng([seed, 1]).uniform(*np.log(n_range), (h, w))
+    st["moment2"][..., 3] = np.exp(st["moment2"][..., 3]).clip(*n_range)
+    if under_moment:
+        ys, xs = np.mgrid[0:h, 0:w]
+        blocks = (xs // 4 + 3 * (ys // 4)) % 10 == 0
+        st["moment2"][..., :3][blocks] = np.float32(0.5) * st["color"][..., :3][blocks] ** 2
+    return st
+
+
+def _cam_args(look_from, look_at, w, h, vup=VUP):
+    return (tuple(look_from), tuple(look_at), tuple(vup), VFOV, w / h, 0.0,
+            float(np.linalg.norm(np.subtract(look_from, look_at))))
+
+
+_Z0 = [dict(p=(0, 0, 0), n=(0, 0, 1))]                     # the plane z = 0
+_GROUND = [dict(p=(0, -1, 0), n=(0, 1, 0))]                # the ground y = -1
+_CORNER = [dict(p=(0, -1, 0), n=(0, 1, 0)),                # a floor, a back wall that ends at y = 0.9 (sky above)
+           dict(p=(0, 0, -2), n=(0, 0, 1), lo=(-99, -99, -99), hi=(99, 0.9, 99)),
+           dict(p=(0, 0, 1), n=(0, 0, 1), lo=(-0.9, -0.6, -99), hi=(0.5, 0.35, 99))]   # and a nearer occluder
+DESIGNED_SIZE = (37, 21)
+DESIGNED_POS_TOL = 0.15
+DESIGNED_CASES = ("shift", "same", "behind", "sideways", "half_off", "horizon", "corner", "moments")
+
+
+def designed_runs(case):
+    """The runs of one designed case: dicts of label, w, h, planes, cam / prev_cam (look_from, look_at
+    [, vup]; prev_cam None: the same camera, passed as the same bits), prev (make_prev's options) and
+    params (step's). pos_tol is DESIGNED_POS_TOL: at this size a pixel's footprint on the plane is
+    0.055 of its distance, more than the default 0.05, which would reject most neighbouring taps."""
+    def run(label, w, h, planes, cam, prev_cam, prev=None, **params):
+        return dict(label=f"{case} {label}".strip(), w=w, h=h, planes=planes, cam=cam, prev_cam=prev_cam,
+                    prev=prev or {}, params=dict(dict(pos_tol=DESIGNED_POS_TOL), **params))
+    w, h = DESIGNED_SIZE
+    eye, origin = (0.0, 0.0, 3.0), (0.0, 0.0, 0.0)
+    sizes = ((w, h, DESIGNED_POS_TOL), (33, 9, 0.4))   # 33 wide: a 32-wide block and one more column; 9 rows: larger pixels
+    if case == "shift":
+        return [run(f"{a}x{b}", a, b, _Z0, (eye, origin), ((0.1, 0.05, 3.0), origin), pos_tol=t) for a, b, t in sizes]
+    if case == "same":
+        return [run(f"{a}x{b}", a, b, _Z0, (eye, origin), None, pos_tol=t) for a, b, t in sizes]
+    if case == "behind":       # the previous camera stood behind the plane and looked away from it
+        return [run("", w, h, _Z0, (eye, origin), ((0.0, 0.0, -3.0), (0.0, 0.0, -6.0)), cur_scale=2.0)]
+    if case == "sideways":
+        return [run("", w, h, _Z0, (eye, origin), ((40.0, 0.0, 3.0), (40.0, 0.0, 0.0)), cur_scale=2.0)]
+    if case == "half_off":
+        # to the side: two taps inside along the seam. From 12 units away with the previous image's
+        # lower left corner at the origin: 4 x 4 pixels per previous pixel, so a dozen share
+        # the corner cell and its single tap inside (pos_tol widened to the previous footprint).
+        # (Three taps inside cannot be: the previous image is a rectangle in its own pixels.)
+        half = 12.0 * np.tan(np.radians(VFOV / 2))
+        far = (half * w / h, half, 12.0)
+        return [run("side", w, h, _Z0, (eye, origin), ((1.5, 0.0, 3.0), (1.5, 0.0, 0.0))),
+                run("corner", w, h, _Z0, (eye, origin), (far, far[:2] + (0.0,)), pos_tol=0.5)]
+    if case == "horizon":
+        # level: the middle row's centre rays lie in the horizon (grazing where the jittered ray hit
+        # the ground); tilted up by 0.08 px: they pass above it (lambda <= 0 there)
+        tilted = (eye, (0.0, 0.08 * 2 * 3.0 * np.tan(np.radians(VFOV / 2)) / h, 0.0))
+        return [run("same camera", w, h, _GROUND, (eye, origin), None),
+                run("shift", w, h, _GROUND, tilted, ((0.1, 0.05, 3.0), origin))]
+    if case == "corner":
+        return [run("", w, h, _CORNER, (eye, origin), ((0.45, 0.3, 3.0), (0.1, 0.1, 0.0)))]
+    if case == "moments":
+        return [run("", w, h, _Z0, (eye, origin), ((0.1, 0.05, 3.0), origin),
+                    prev=dict(n_range=(1.0, 40.0), under_moment=True))]
+    raise ValueError(f"unknown designed case {case!r}")
+
+
+def designed_inputs(run, make_camera, seed=0):
+    """(color, cur, prev, camera, prev_camera) of one designed run; the feature buffers hold their
+    values / cur_scale, as a frame accumulated over cur_scale samples does."""
+    w, h = run["w"], run["h"]
+    cam = make_camera(*_cam_args(*run["cam"][:2], w, h, *run["cam"][2:]))
+    pcam = cam if run["prev_cam"] is None else make_camera(*_cam_args(*run["prev_cam"][:2], w, h, *run["prev_cam"][2:]))
+    color, cur, _ = plane_frame(w, h, cam, run["planes"], [seed, w, h, 0])
+    _, g0, _ = plane_frame(w, h, pcam, run["planes"], [seed, w, h, 1])
+    prev = make_prev({k: g0[k] for k in ("normal", "world_pos")}, 1000 * w + h + seed, **run["prev"])
+    k = np.float32(run["params"].get("cur_scale", 1.0))
+    return color / k, {n: v / k for n, v in cur.items()}, prev, cam, pcam
+
+
+def designed_gap(make_camera):
+    """f32_f64_gap over the designed cases: (all outputs but color_std, color_std, {run: fragile share})."""
+    worst, worst_std, shares = 0.0, 0.0, {}
+    for case in DESIGNED_CASES:
+        for run in designed_runs(case):
+            color, cur, prev, cam, pcam = designed_inputs(run, make_camera)
+            a, fa = step(color, cur, prev, cam, pcam, np.float32, **run["params"])
+            b, fb = step(color, cur, prev, cam, pcam, np.float64, **run["params"])
+            ok = ~(fa | fb)
+            shares[run["label"]] = float(fb.mean())
+            for name in OUTPUTS:
+                g = rel_gap(a[name], b[name], ok)
+                if name == "color_std":
+                    worst_std = max(worst_std, g)
+                else:
+                    worst = max(worst, g)
+    return worst, worst_std, shares
+
+
 if __name__ == "__main__":
     import os
     import sys
@@ -264,3 +442,7 @@ if __name__ == "__main__":
     print(f"largest f32 - f64 gap over the GPU test's cases: {gap:.3g} (color_std: {gap_std:.3g})")
     for (w, h, dt), s in shares.items():
         print(f"  {w}x{h} step {dt}: fragile {100 * s:.2f} %")
+    gap, gap_std, shares = designed_gap(make_camera)
+    print(f"largest f32 - f64 gap over the designed cases: {gap:.3g} (color_std: {gap_std:.3g})")
+    for label, s in shares.items():
+        print(f"  {label}: fragile {100 * s:.2f} %")

@@ -153,6 +153,79 @@ def test_restatement_null_guides_drop_their_terms():
     assert np.array_equal(a, R.atrous(color, {"normal": guides["normal"]}, np.float64))
 
 
+SYNTHETIC_67x45_SHA256 = dict(          # the first 16 hex digits, from before synthetic_inputs took variant=
+    color="2bb1ff2d8af43b53", albedo="62fa4bcf6e119588", color_std="d09e2577683e6718",
+    normal="b8566b37d1ca083c", world_pos="b7e0acce522f24a7")
+F32_F64_GAP_EDGE = 9.9e-7               # tests/test_gpu_denoise.py's
+
+
+def test_synthetic_inputs_default_is_unchanged():
+    import hashlib
+    color, guides = R.synthetic_inputs(67, 45)
+    for name, a in dict(guides, color=color).items():
+        assert a.dtype == np.float32 and a.shape == (45, 67, 4)
+        assert hashlib.sha256(a.tobytes()).hexdigest()[:16] == SYNTHETIC_67x45_SHA256[name], name
+    again, _ = R.synthetic_inputs(67, 45, variant=None)
+    assert np.array_equal(again, color)
+    with pytest.raises(ValueError):
+        R.synthetic_inputs(67, 45, variant="nope")
+
+
+def test_edge_table_is_what_the_gpu_test_quotes():
+    sweeps = R.edge_sweeps()
+    table = R.edge_table()
+    assert 50 <= len(table) <= 150 and len(table) == sum(len(c) for c in sweeps.values())
+    assert {(c["w"], c["h"]) for c in table} == set(R.EDGE_SHAPES) | {R.EDGE_BASE, R.EDGE_WIDE}
+    w, h = R.EDGE_WIDE           # more workgroups than 256 CUs x 8 hold, the second row group's far behind the first's
+    assert sweeps["wide"][0]["params"]["iterations"] == 5 and h > 32 and (w // 64) * 8 >= 2048
+    for w, h in R.EDGE_SHAPES:
+        assert [c["params"]["iterations"] for c in sweeps[f"shape_{w}x{h}"]] == [3, 4, 5]
+    assert sorted(c["guides"] for c in sweeps["guides"]) == sorted(
+        [(g,) for g in L.GUIDE_NAMES] + [tuple(n for n in R.GUIDE_SETS["all"] if n != g) for g in L.GUIDE_NAMES])
+    assert len(set(R.EDGE_SIGMAS_ALL.values())) == 4 and set(R.EDGE_SIGMAS_ALL) == set(R.SIGMAS)
+    assert [c["variant"] for c in sweeps["variants"]] == list(R.VARIANTS)
+    assert len(R.default_table()) == len(R.SHAPES) * len(R.ITERATIONS) * len(R.GUIDE_SETS)
+
+
+@pytest.mark.parametrize("variant", R.VARIANTS)
+def test_variant_inputs_and_their_restatement(variant):
+    """Each variant is what it says, touches nothing else, and the f32 restatement of it is finite
+    and within the recorded gap of the f64 one."""
+    w, h = R.EDGE_BASE
+    base_c, base_g = R.synthetic_inputs(w, h)
+    color, guides = R.synthetic_inputs(w, h, variant=variant)
+    changed = {"std_extremes": "color_std", "fireflies": "color", "far_origin": "world_pos"}.get(variant)
+    for name, a in dict(guides, color=color).items():
+        b = dict(base_g, color=base_c)[name]
+        if name != changed:
+            assert np.array_equal(a[..., :3], b[..., :3]), name
+        if variant != "dirty_alpha" or name == "color":
+            assert np.array_equal(a[..., 3], b[..., 3]), name
+    if variant == "std_extremes":
+        std = guides["color_std"][..., :3]
+        zero, big = (std == 0).all(-1), (std == np.float32(1e3)).all(-1)
+        assert 0.25 < zero.mean() < 0.42 and 0.25 < big.mean() < 0.42 and not (zero & big).any()
+        assert np.array_equal(std[~(zero | big)], base_g["color_std"][..., :3][~(zero | big)])
+    elif variant == "fireflies":
+        hot = (color[..., :3] > 4).all(-1)
+        assert hot.sum() == 6 and (color[..., :3] == 65504.0).all(-1).sum() == 1
+        assert ((color[..., :3] == 1e4).all(-1)).sum() == 5
+    elif variant == "dirty_alpha":
+        for name, g in guides.items():
+            al = g[..., 3]
+            assert np.isnan(al).sum() > 100 and np.isposinf(al).sum() > 100 and (al == np.float32(1e30)).sum() > 100, name
+        assert np.isfinite(color).all()
+    else:
+        shift = guides["world_pos"][..., :3] - base_g["world_pos"][..., :3]
+        assert np.abs(shift - np.float32(R.FAR_ORIGIN)).max() <= 1e-4          # (the f32 sum rounds at 6e-5)
+    a32 = R.atrous(color, guides, np.float32)
+    a64 = R.atrous(color, guides, np.float64)
+    assert a32.dtype == np.float32 and np.isfinite(a32).all() and np.isfinite(a64).all()
+    assert R.rel_gap(a32, a64) <= F32_F64_GAP_EDGE
+    if variant == "dirty_alpha":
+        assert np.array_equal(a64, R.atrous(base_c, base_g, np.float64))
+
+
 def test_denoise_bench_byte_count():
     """tools/denoise_bench.py's bytes per pass, from the tile geometry: a frame of exactly one tile
     stages itself once; a large frame stages ~2.1x (s = 1) to ~4x (s = 16) its pixels; never less

@@ -7,7 +7,10 @@ The filter is tolerance-checked, not bit-pinned (the reference has no such filte
 contract and uses the hardware exp). Bound: |got - f64| <= TOL * max(1, |f64|) at every pixel, TOL
 = 16 x the largest gap between the restatement's own f32 and f64 runs over these same cases
 (`python tests/denoise_ref.py` measures it on the CPU); the 16x allows for another exp and
-another summation order."""
+another summation order. The edge table (tests/denoise_ref.py, edge_sweeps()) is judged by the same
+rule with the gap measured over its own cases. Measured on the GPU: at most 7.6e-7 over the edge table
+(0.05 of its bound); far_origin 6.0e-7 (4.98e-5, 3.1 x the bound, before world_pos was staged
+relative to a per-workgroup anchor)."""
 import numpy as np
 import pytest
 
@@ -17,6 +20,8 @@ pytestmark = pytest.mark.gpu
 
 F32_F64_GAP = 9.5e-7          # measured: 9.5e-07 (tests/denoise_ref.py, f32_f64_gap())
 TOL = 16 * F32_F64_GAP
+F32_F64_GAP_EDGE = 9.9e-7     # measured: 9.86e-07 (tests/denoise_ref.py, f32_f64_gap(edge_table()))
+TOL_EDGE = 16 * F32_F64_GAP_EDGE
 
 
 def _bits(a):
@@ -37,6 +42,61 @@ def test_denoise_vs_restatement(gpu, w, h):
             worst = max(worst, gap)
             assert np.isfinite(got).all() and gap <= TOL, f"{w}x{h} iterations={it} guides={label}: {gap:.3g} > {TOL:.3g}"
     print(f"{w}x{h}: largest gap {worst:.3g} (bound {TOL:.3g})")
+
+
+EDGE_SWEEPS = R.edge_sweeps()
+
+
+@pytest.mark.parametrize("sweep", list(EDGE_SWEEPS))
+def test_denoise_edges_vs_restatement(gpu, sweep):
+    """The edge table: the shapes on and beside the 64-row group and the 64-column tile at the three
+    ping-pong parities, every iteration count, single and leave-one-out guide sets, other sigmas
+    and the input variants (far_origin among them, by the same bound), and one frame of more
+    workgroups than the device holds at once. Every pixel, no exclusions."""
+    worst = 0.0
+    for c in EDGE_SWEEPS[sweep]:
+        color, g = R.case_inputs(c)
+        got = gpu.denoise_host(color, g, **c["params"])
+        want = R.atrous(color, g, np.float64, **c["params"])
+        assert np.array_equal(_bits(got[..., 3]), _bits(color[..., 3]))
+        gap = R.rel_gap(got[..., :3], want)
+        worst = max(worst, gap)
+        print(f"{R.case_label(c)}: gap {gap:.3g} ({gap / TOL_EDGE:.3f} of the bound)")
+        assert np.isfinite(got).all() and gap <= TOL_EDGE, f"{R.case_label(c)}: {gap:.3g} > {TOL_EDGE:.3g}"
+        if c["variant"] == "dirty_alpha":       # a guide's alpha is never read
+            clean, cg = R.case_inputs(dict(c, variant=None))
+            assert np.array_equal(_bits(clean), _bits(color))
+            assert np.array_equal(_bits(gpu.denoise_host(clean, cg, **c["params"])), _bits(got))
+    print(f"{sweep}: largest gap {worst:.3g} (bound {TOL_EDGE:.3g})")
+
+
+def test_denoise_scratch_grows_across_two_streams(gpu):
+    """Two non-default streams with scratch of their own: on A 19x13, then 129x65 (its scratch has
+    to grow), then 19x13 again, all at K = 5, with other inputs enqueued on B between them and a
+    K = 1 in-place call (the copy path) on each; one synchronisation per stream at the end. Every
+    result is lrt_denoise_host's of the same inputs, bit for bit."""
+    import torch
+    dev = torch.device("cuda:0")
+    A, B = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    plan = [(A, 19, 13, 0, 5, False), (B, 67, 45, 1, 5, False), (A, 129, 65, 0, 5, False), (B, 19, 13, 2, 3, False),
+            (B, 65, 8, 1, 1, True), (A, 19, 13, 3, 5, False), (A, 129, 65, 4, 1, True), (B, 129, 65, 5, 4, False)]
+    up = lambda a: torch.from_numpy(a).to(dev)   # noqa: E731
+    staged = []
+    for s, w, h, seed, it, inplace in plan:
+        color, guides = R.synthetic_inputs(w, h, seed=seed)
+        tc = up(color)
+        out = tc if inplace else torch.full((h, w, 4), 7.0, device=dev)    # 7: the alpha sentinel
+        staged.append((color, guides, tc, {k: up(v) for k, v in guides.items()}, out))
+    torch.cuda.synchronize()                      # the uploads (default stream) are done before A and B start
+    for (s, w, h, seed, it, inplace), (_, _, tc, tg, out) in zip(plan, staged):
+        assert gpu.denoise_tensor(tc, tg, out=out, stream=s, iterations=it) is out
+    A.synchronize()
+    B.synchronize()
+    for (s, w, h, seed, it, inplace), (color, guides, _, _, out) in zip(plan, staged):
+        want = gpu.denoise_host(color, guides, iterations=it)
+        got = out.cpu().numpy()
+        assert np.array_equal(_bits(got[..., :3]), _bits(want[..., :3])), (w, h, seed, it, inplace)
+        assert np.array_equal(got[..., 3], color[..., 3]) if inplace else (got[..., 3] == 7.0).all()
 
 
 @pytest.mark.parametrize("it", [1, 2, 5])

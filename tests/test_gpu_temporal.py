@@ -11,7 +11,9 @@ result, not an error), TOL = 16 x the largest gap between the restatement's own 
 these same cases (`python tests/temporal_ref.py` measures it on the CPU). The gap is that large
 because a reprojected position carries ~1e-5 px of f32 rounding, which the bilinear weights turn
 into that share of the difference between neighbouring history values (random, of order 1, here).
-Measured on the GPU: at most 0.061 of the bound (160x90), 8e-8 of it at 1x1."""
+Measured on the GPU: at most 0.061 of the bound (160x90), 8e-8 of it at 1x1. The designed plane
+scenes (test_step_designed_cases) follow the same rule with the gap measured over themselves, a
+tenth of the orbit's; measured on the GPU: at most 0.062 of that bound (`moments`)."""
 import numpy as np
 import pytest
 
@@ -24,6 +26,11 @@ F32_F64_GAP = 2.5e-4          # measured: 2.43e-04 (tests/temporal_ref.py, f32_f
 F32_F64_GAP_STD = 1.6e-4      # measured: 1.53e-04, color_std (a square root of a cancelling difference)
 TOL, TOL_STD = 16 * F32_F64_GAP, 16 * F32_F64_GAP_STD
 MAX_FRAGILE = 0.02
+# the designed plane scenes (tests/temporal_ref.py, designed_gap()): no rendered geometry, few fragile
+# pixels, so the same rule gives a bound an order of magnitude tighter than the orbit's
+F32_F64_GAP_DESIGNED = 2.5e-5       # measured: 2.47e-05, all outputs but color_std
+F32_F64_GAP_STD_DESIGNED = 4.8e-5   # measured: 4.71e-05, color_std (`moments`: roots next to the variance clamp)
+TOL_DESIGNED, TOL_STD_DESIGNED = 16 * F32_F64_GAP_DESIGNED, 16 * F32_F64_GAP_STD_DESIGNED
 CUR = ("normal", "world_pos", "albedo")
 
 
@@ -79,6 +86,38 @@ def test_step_vs_restatement(gpu, w, h):
             worst = max(worst, gap / _tol(name))
             assert gap <= _tol(name), f"{w}x{h} step {dt} {name}: {gap:.3g} > {_tol(name):.3g}"
     print(f"{w}x{h}: largest gap {worst:.3g} of its bound")
+
+
+@pytest.mark.parametrize("case", R.DESIGNED_CASES)
+def test_step_designed_cases(gpu, case):
+    """Plane scenes and camera pairs built so that each branch of the step holds pixels (counted on
+    the CPU by tests/test_temporal_cpu.py::test_designed_cases_cover_their_branches): every output
+    against the f64 restatement on the non-fragile pixels, and n = 1 exactly wherever the f64
+    decision is to reset."""
+    worst = 0.0
+    for run in R.designed_runs(case):
+        color, cur, prev, cam, pcam = R.designed_inputs(run, gpu.make_camera)
+        got = _outputs(gpu.temporal_accumulate_host(color, cur, prev, cam, pcam, **run["params"]))
+        info = {}
+        want, fragile = R.step(color, cur, prev, cam, pcam, np.float64, info=info, **run["params"])
+        assert fragile.mean() <= MAX_FRAGILE
+        reset = ~info["keep"] & ~fragile
+        print(f"{run['label']}: fragile {100 * fragile.mean():.2f} %, history kept at {100 * info['keep'].mean():.0f} %")
+        assert (got["n"][reset] == 1).all()
+        if case in ("behind", "sideways"):
+            k = np.float32(run["params"]["cur_scale"])
+            assert reset.all() and np.array_equal(_bits(got["color"]), _bits(k * color[..., :3]))
+            assert (got["color_std"] == np.float32(R.DEFAULTS["short_std"])).all()
+        if case == "same":
+            assert info["keep"].all() and (got["n"] > 1).all()
+        for name in R.OUTPUTS:
+            tol = TOL_STD_DESIGNED if name == "color_std" else TOL_DESIGNED
+            assert np.isfinite(got[name]).all(), name
+            gap = R.rel_gap(got[name], want[name], ~fragile)
+            worst = max(worst, gap / tol)
+            print(f"  {name}: gap {gap:.3g} ({gap / tol:.3f} of its bound)")
+            assert gap <= tol, f"{run['label']} {name}: {gap:.3g} > {tol:.3g}"
+    print(f"{case}: largest gap {worst:.3g} of its bound")
 
 
 @pytest.fixture(scope="module")

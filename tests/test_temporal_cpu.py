@@ -288,6 +288,130 @@ def test_alpha_channels():
     assert np.array_equal(st["moment2"][..., 3], np.float32(out["n"])) and (st["color"][..., 3] == 0).all()
 
 
+# ---- the designed scenes
+MAX_FRAGILE = 0.02            # tests/test_gpu_temporal.py's
+F32_F64_GAP_DESIGNED, F32_F64_GAP_STD_DESIGNED = 2.5e-5, 4.8e-5   # tests/test_gpu_temporal.py's
+
+
+def _n(mask):
+    return int(np.count_nonzero(mask))
+
+
+# what each case is there for: {run label: [(branch, pixels of it in the f64 info, at least)]}
+DESIGNED_BRANCHES = {
+    "shift 37x21": [("kept", lambda i: i["keep"], 0.98 * 37 * 21), ("four taps inside", lambda i: i["taps_inside"] == 4, 8)],
+    "shift 33x9": [("kept", lambda i: i["keep"], 0.95 * 33 * 9), ("kept with four taps inside", lambda i: i["keep"] & (i["taps_inside"] == 4), 8)],
+    "same 37x21": [("kept", lambda i: i["keep"], 37 * 21)],
+    "same 33x9": [("kept", lambda i: i["keep"], 33 * 9), ("column 32 kept", lambda i: i["keep"][:, 32], 9)],
+    "behind": [("not projectable", lambda i: ~i["ok"], 37 * 21), ("reset", lambda i: ~i["keep"], 37 * 21)],
+    "sideways": [("projectable, no tap inside", lambda i: i["ok"] & (i["taps_inside"] == 0), 37 * 21),
+                 ("reset", lambda i: ~i["keep"], 37 * 21)],
+    "half_off side": [("kept", lambda i: i["keep"], 0.7 * 37 * 21), ("reset", lambda i: ~i["keep"], 0.2 * 37 * 21),
+                      ("two taps inside", lambda i: i["taps_inside"] == 2, 8),
+                      ("no tap inside", lambda i: i["taps_inside"] == 0, 8)],
+    "half_off corner": [("one tap inside", lambda i: i["taps_inside"] == 1, 8),
+                        ("one tap inside, kept", lambda i: (i["taps_inside"] == 1) & i["keep"], 8),
+                        ("two taps inside", lambda i: i["taps_inside"] == 2, 8)],
+    "horizon same camera": [("miss", lambda i: ~i["hit"], 8), ("grazing", lambda i: i["grazing"], 8),
+                            ("hit, not centred (the same-camera shortcut declined)", lambda i: i["hit"] & ~i["centred"], 8),
+                            ("miss kept (onto misses)", lambda i: ~i["hit"] & i["keep"], 8),
+                            ("miss onto hit rejected", lambda i: ~i["hit"] & (i["rej_hitmiss"] > 0), 8)],
+    "horizon shift": [("miss", lambda i: ~i["hit"], 8), ("lambda <= 0", lambda i: i["lam_le0"], 8),
+                      ("miss kept (onto misses)", lambda i: ~i["hit"] & i["keep"], 8),
+                      ("hit onto miss rejected", lambda i: i["hit"] & (i["rej_hitmiss"] > 0), 8)],
+    "corner": [("rejected by normal alone", lambda i: i["rej_normal"] > 0, 4),
+               ("rejected by position alone", lambda i: i["rej_pos"] > 0, 4),
+               ("rejected by hit / miss", lambda i: i["rej_hitmiss"] > 0, 4),
+               ("taps inside, all rejected", lambda i: (i["taps_inside"] > 0) & ~i["keep"], 8)],
+    "moments": [("variance clamped", lambda i: i["var_clamped"], 8), ("variance not clamped", lambda i: i["keep"] & ~i["var_clamped"], 8),
+                ("alpha clamped", lambda i: i["alpha_clamped"], 8), ("alpha not clamped", lambda i: i["keep"] & ~i["alpha_clamped"], 8),
+                ("short history", lambda i: i["short_history"], 8), ("long history", lambda i: ~i["short_history"], 8)],
+}
+
+
+def test_designed_cases_cover_their_branches():
+    """The designed scenes reach what they are designed for, in the f64 restatement alone: every
+    listed branch holds its pixels, few pixels are fragile, the restatement's own f32 run is within
+    the recorded gap, and over all cases every mask of `info` is populated on both sides."""
+    seen = {name: [0, 0] for name in R.INFO_MASKS + R.INFO_COUNTS}
+    labels = []
+    taps = set()
+    worst, worst_std = 0.0, 0.0
+    for case in R.DESIGNED_CASES:
+        for run in R.designed_runs(case):
+            labels.append(run["label"])
+            color, cur, prev, cam, pcam = R.designed_inputs(run, make_camera)
+            assert (pcam is cam) == (run["prev_cam"] is None)
+            info = {}
+            out, fragile = R.step(color, cur, prev, cam, pcam, np.float64, info=info, **run["params"])
+            plain, fragile2 = R.step(color, cur, prev, cam, pcam, np.float64, **run["params"])
+            for name in R.OUTPUTS:                       # info= changes nothing
+                assert np.array_equal(out[name], plain[name]), name
+            assert np.array_equal(fragile, fragile2)
+            assert set(info) == set(R.INFO_MASKS + R.INFO_COUNTS)
+            assert fragile.mean() <= MAX_FRAGILE, run["label"]
+            for what, mask, least in DESIGNED_BRANCHES[run["label"]]:
+                print(f"{run['label']}: {what}: {_n(mask(info))} (>= {least:g})")
+                assert _n(mask(info)) >= least, (run["label"], what)
+            for name in seen:
+                seen[name][0] += _n(info[name])
+                seen[name][1] += _n(info[name] == 0)
+            taps |= set(np.unique(info["taps_inside"]).tolist())
+            # the masks say what the outputs say
+            assert np.array_equal(info["keep"], out["n"] > 1)
+            assert (out["n"][~info["keep"]] == 1).all()
+            assert np.array_equal(info["short_history"], (out["color_std"] == 1e3).all(-1))
+            assert (out["color_std"][info["var_clamped"] & ~info["short_history"]] == 0).any(-1).all()
+            f32, ff = R.step(color, cur, prev, cam, pcam, np.float32, **run["params"])
+            for name in R.OUTPUTS:
+                g = R.rel_gap(f32[name], out[name], ~(fragile | ff))
+                if name == "color_std":
+                    worst_std = max(worst_std, g)
+                else:
+                    worst = max(worst, g)
+    assert sorted(labels) == sorted(DESIGNED_BRANCHES)
+    for name, (on, off) in seen.items():
+        assert on > 0 and off > 0, name
+    assert taps == {0, 1, 2, 4}                           # (three cannot be: the previous image is a rectangle)
+    print(f"f32 - f64 over the designed cases: {worst:.3g} (color_std: {worst_std:.3g})")
+    assert worst <= F32_F64_GAP_DESIGNED and worst_std <= F32_F64_GAP_STD_DESIGNED
+
+
+def test_plane_frame_and_make_prev():
+    w, h = R.DESIGNED_SIZE
+    run = R.designed_runs("corner")[0]
+    color, cur, prev, cam, pcam = R.designed_inputs(run, make_camera)
+    c2, f2, hit = R.plane_frame(w, h, cam, run["planes"], [0, w, h, 0])
+    assert np.array_equal(c2, color) and all(np.array_equal(f2[k], cur[k]) for k in cur)
+    assert 0.2 < hit.mean() < 0.9 and color.dtype == np.float32 and (color[..., :3] >= 0.05).all()
+    n2 = (cur["normal"][..., :3] ** 2).sum(-1)
+    assert np.allclose(n2[hit], 1, atol=1e-6) and (n2[~hit] == 0).all() and (cur["world_pos"][~hit] == 0).all()
+    pos, O = np.float64(cur["world_pos"][..., :3]), np.float64(R.cam22(cam)[:3])
+    on_plane = [np.abs((pos - np.float64(pl["p"])) @ np.float64(pl["n"])) < 1e-5 for pl in run["planes"]]
+    assert np.logical_or.reduce(on_plane)[hit].all() and all(8 <= _n(m & hit) for m in on_plane)
+    assert (((O - pos) * cur["normal"][..., :3]).sum(-1)[hit] > 0).all()         # turned towards the camera
+    # the hit point lies within JITTER px of the pixel centre as the camera sees it
+    c = np.float64(R.cam22(cam))
+    L, H, V = c[12:15], c[15:18], c[18:21]
+    d = pos - O
+    q = d * ((L - O) @ c[3:6] / (d @ c[3:6]))[..., None] - (L - O)
+    ys, xs = np.mgrid[0:h, 0:w]
+    fx, fy = q @ H / (H @ H) * w - 0.5 - xs, q @ V / (V @ V) * h - 0.5 - ys
+    assert np.abs(fx[hit]).max() <= R.JITTER + 1e-4 and np.abs(fy[hit]).max() <= R.JITTER + 1e-4
+    assert np.abs(fx[hit]).max() > 0.2
+    # make_prev: random_prev but for n and, on a tenth of the pixels, the moment
+    base = R.random_prev(cur, 5)
+    st = R.make_prev(cur, 5, n_range=(1.0, 40.0), under_moment=True)
+    assert all(np.array_equal(st[k], base[k]) for k in ("color", "normal", "world_pos"))
+    n = st["moment2"][..., 3]
+    assert n.min() >= 1 and n.max() <= 40 and n.max() > 30
+    under = (st["moment2"][..., :3] < st["color"][..., :3] ** 2).all(-1)
+    assert 0.05 < under.mean() < 0.15
+    assert np.array_equal(st["moment2"][..., :3][~under], base["moment2"][..., :3][~under])
+    assert np.array_equal(st["moment2"][..., :3][under], np.float32(0.5) * st["color"][..., :3][under] ** 2)
+    assert np.array_equal(R.make_prev(cur, 5)["moment2"][..., :3], base["moment2"][..., :3])
+
+
 # ---- what it is for
 @pytest.fixture(scope="module")
 def ground_truth():
