@@ -317,7 +317,9 @@ int lrt_present_bgra8(const float* d_rgba, uint32_t* d_bgra, int width, int heig
  * Whole frames only: every buffer is height rows of width RGBA float quads. A
  * row-block-cyclic shard (row_period > 1) lacks its rows' neighbours and cannot be filtered
  * on its own -- assemble the frame first. No temporal reuse of its own (lrt_temporal_* below is
- * the stage for that), no albedo demodulation, and the variance guide itself is not filtered. */
+ * the stage for that). This filter does not demodulate albedo and reads color_std as it is, the
+ * same value at every pass; lrt_svgf_* (further below) is the filter that divides albedo out and
+ * filters and propagates the variance, from the temporal state directly. */
 #define LRT_DENOISE_MAX_ITER 5
 typedef struct lrt_denoise_desc {
     int32_t width, height;      /* a whole frame: height rows of width RGBA float quads */
@@ -445,6 +447,72 @@ int lrt_temporal_accumulate_device(const lrt_temporal_desc* desc, const float* d
 int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* color, const lrt_features* cur,
                                  const lrt_temporal_state* prev, const lrt_temporal_state* next,
                                  float* color_std);
+
+/* ---- variance-guided filter over the temporal state ------------------------------ */
+
+/* Stages 2 and 3 of SVGF (Schied et al. 2017) on the state lrt_temporal_accumulate_* leaves:
+ * estimate each pixel's variance (from its temporal moments, or from its neighbourhood where
+ * the history is short), divide the albedo out, and run `iterations` a-trous passes whose
+ * colour weight follows the variance, which is itself pre-filtered and propagated from pass to
+ * pass. All buffers are whole frames: `height` rows of `width` RGBA float quads. f32 throughout.
+ *
+ * Stage 0, per pixel p, with C = color.rgb, M = moment2.rgb, n = moment2.a:
+ *     hit = |N|^2 >= 0.25 if normal is given, else true
+ *     D   = max(A, albedo_floor) per channel if albedo is given and hit, else 1
+ *     v   = max(M - C^2, 0)                                        if n >= min_history
+ *         = max(m2 - m1^2, 0) * (min_history / max(n, 1))           otherwise, with
+ *           m1 = sum_q g C(q) / sum_q g, m2 = sum_q g M(q) / sum_q g over the 7x7 window
+ *           q = p + (i, j), i, j in -3..3 (taps outside the image are skipped),
+ *           g(p,q) = exp(-(|n(p) - n(q)|^2 / sigma_normal^2 + |x(p) - x(q)|^2 / sigma_pos^2))
+ *           (a term is dropped if its guide is absent)
+ *     c_0 = C / D, var_0 = v / D^2
+ * Passes k = 0 .. iterations - 1, with the 5x5 B3-spline taps q = p + 2^k (i, j), i, j in -2..2,
+ * h = [1/16, 1/4, 3/8, 1/4, 1/16], as in lrt_denoise_*; taps outside the image are skipped:
+ *     vt(p) = sum_{|i|,|j| <= 1} b_i b_j var_k(p + (i, j)) / sum b_i b_j,  b = [1/4, 1/2, 1/4]
+ *             (undilated at every pass; only the taps inside the image count)
+ *     E(p,q) = |c_k(p) - c_k(q)|^2 / (sigma_color^2 (vt.r + vt.g + vt.b) + 1e-6)
+ *            + |n(p) - n(q)|^2 / sigma_normal^2 + |x(p) - x(q)|^2 / sigma_pos^2
+ *     w = h[i] h[j] exp(-E)
+ *     c_{k+1}(p) = sum_q w c_k(q) / sum_q w,  var_{k+1}(p) = sum_q w^2 var_k(q) / (sum_q w)^2
+ * There is no albedo term (albedo is divided out instead) and sigma_color is the same at every
+ * pass (the variance shrinks by itself). End: out.rgb = c_K D, variance_out.rgb = var_K D^2.
+ * The only decisions are n < min_history and hit, both on input values. Deterministic run to
+ * run; tolerance-checked against its NumPy restatement (tests/svgf_ref.py), not bit-pinned. */
+#define LRT_SVGF_MAX_ITER 5
+typedef struct lrt_svgf_desc {
+    int32_t width, height;     /* a whole frame */
+    int32_t iterations;        /* 1..LRT_SVGF_MAX_ITER */
+    int32_t flags;             /* 0 */
+    int32_t min_history;       /* >= 1 */
+    int32_t reserved;          /* 0 */
+    float sigma_color, sigma_normal, sigma_pos;   /* finite, > 0 */
+    float albedo_floor;        /* finite, > 0 */
+} lrt_svgf_desc;
+
+/* The defaults for a width x height frame: 5 iterations, min_history 4, sigma_color 4,
+ * sigma_normal 0.3, sigma_pos 0.5, albedo_floor 0.01. */
+int lrt_svgf_default(int width, int height, lrt_svgf_desc* out);
+
+/* Filter the state's d_color / d_moment2 (the color and moment2 members of an
+ * lrt_temporal_state; moment2's alpha is n) into d_out (device buffers). Of d_guides, normal,
+ * world_pos and albedo are read; each may be NULL, and d_guides may be NULL; the other members
+ * are ignored. d_variance_out may be NULL. Only the rgb of d_out and d_variance_out is written,
+ * their alphas stay. d_out may be d_color (in place); otherwise neither output may overlap an
+ * input or the other output (address ranges; LRT_E_INVALID).
+ *
+ * LRT_E_INVALID, before any device use: NULL desc, color, moment2 or out; sizes < 1 or
+ * width * height > INT_MAX / 4; iterations outside 1..LRT_SVGF_MAX_ITER; flags or reserved != 0;
+ * min_history < 1; a sigma or albedo_floor that is not finite and > 0; aliasing. Then
+ * LRT_E_STATE without lrt_initialize(). Asynchronous on `stream` and ordered only against it;
+ * the intermediate frames live in that stream's scratch of the library. Acts on the first
+ * device. */
+int lrt_svgf_filter_device(const lrt_svgf_desc* desc, const float* d_color, const float* d_moment2,
+                           const lrt_features* d_guides, float* d_out, float* d_variance_out, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; the outputs equal
+ * lrt_svgf_filter_device's bit for bit. */
+int lrt_svgf_filter_host(const lrt_svgf_desc* desc, const float* color, const float* moment2,
+                         const lrt_features* guides, float* out, float* variance_out);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,19 @@ TEMPORAL_STATE_NAMES = ("color", "moment2", "normal", "world_pos", "albedo")
 TEMPORAL_CUR_NAMES = ("normal", "world_pos", "albedo")   # what lrt_temporal_* reads of lrt_features
 TEMPORAL_PARAMS = ("cur_scale", "alpha_min", "normal_min", "pos_tol", "short_std", "min_history")
 
+SVGF_MAX_ITER = 5
+SVGF_GUIDE_NAMES = ("normal", "world_pos", "albedo")   # what lrt_svgf_* reads of lrt_features
+SVGF_PARAMS = ("iterations", "min_history", "sigma_color", "sigma_normal", "sigma_pos", "albedo_floor")
+
+
+class SvgfDesc(ctypes.Structure):             # lrt_svgf_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("iterations", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("min_history", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_pos", ctypes.c_float), ("albedo_floor", ctypes.c_float)]
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -165,6 +178,9 @@ SIGNATURES = {
                                             _c.POINTER(TemporalState), _c.POINTER(TemporalState), _vp, _vp]),
     "lrt_temporal_accumulate_host": (_i, [_c.POINTER(TemporalDesc), _vp, _c.POINTER(Features),
                                           _c.POINTER(TemporalState), _c.POINTER(TemporalState), _vp]),
+    "lrt_svgf_default": (_i, [_i, _i, _c.POINTER(SvgfDesc)]),
+    "lrt_svgf_filter_device": (_i, [_c.POINTER(SvgfDesc), _vp, _vp, _c.POINTER(Features), _vp, _vp, _vp]),
+    "lrt_svgf_filter_host": (_i, [_c.POINTER(SvgfDesc), _vp, _vp, _c.POINTER(Features), _vp, _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

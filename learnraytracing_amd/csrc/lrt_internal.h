@@ -11,6 +11,7 @@
 //   lrt_frame.hip     frame assembly and present kernels
 //   lrt_denoise.hip   the feature-guided a-trous denoiser (lrt_denoise_*): kernel and entry points
 //   lrt_temporal.hip  temporal reprojection and accumulation (lrt_temporal_*): kernel and entry points
+//   lrt_svgf.hip      the variance-guided filter over the temporal state (lrt_svgf_*): kernels and entry points
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
 #pragma once

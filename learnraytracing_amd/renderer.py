@@ -541,6 +541,99 @@ class TemporalAccumulator:
         self._camera = L.Camera.from_buffer_copy(camera)
         return nxt["color"], {k: nxt[k] for k in L.GUIDE_NAMES if k in out}
 
+    @property
+    def state(self) -> dict:
+        """The state the last step wrote, {"color", "moment2", "normal", "world_pos", "albedo"}: the
+        accumulator's own tensors, valid until the step after the next; read-only (a new dict each
+        time). svgf_filter_tensor(acc.state["color"], acc.state["moment2"], guides) chains on the
+        step's stream."""
+        return {k: self._states[self._cur][k] for k in L.TEMPORAL_STATE_NAMES}
+
+
+# ---- variance-guided filter over the temporal state ----------------------------------------
+def svgf_desc(width: int, height: int, **params) -> L.SvgfDesc:
+    """lrt_svgf_default for a width x height frame, with any of iterations, min_history,
+    sigma_color, sigma_normal, sigma_pos, albedo_floor overridden."""
+    d = L.SvgfDesc()
+    L.check(L.lib().lrt_svgf_default(int(width), int(height), ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.SVGF_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown svgf parameter {name!r}")
+        setattr(d, name, int(v) if name in ("iterations", "min_history") else float(v))
+    return d
+
+
+def svgf_filter_host(color: np.ndarray, moment2: np.ndarray, guides: Optional[dict],
+                     out: Optional[np.ndarray] = None, variance_out: Optional[np.ndarray] = None, **params):
+    """Filter a temporal state with the variance-guided a-trous filter (lrt_svgf_filter_host).
+    color, moment2: the state's members, float32 [height, width, 4] (or flat with width=,
+    height=), the history length in moment2's alpha; guides: {name: buffer} with "normal",
+    "world_pos", "albedo" (a missing one drops its term; None or {}: no guides; the other
+    lrt_features names are accepted and not read, so that step()'s guides pass as they are). out: the
+    destination (may be color; only its rgb is written), default a copy of color. variance_out:
+    if given, receives the filtered variance (rgb only). params: iterations, min_history,
+    sigma_color, sigma_normal, sigma_pos, albedo_floor. Returns out."""
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = svgf_desc(w, h, **params)
+    n = w * h * 4
+    _check_host_buffer(color, n)
+    _check_host_buffer(moment2, n)
+    if out is None:
+        out = color.copy()
+    _check_host_buffer(out, n)
+    if variance_out is not None:
+        _check_host_buffer(variance_out, n)
+    f = L.Features()
+    for name, buf in (guides or {}).items():
+        if name not in L.FEATURE_NAMES:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown guide {name!r}")
+        if name not in L.SVGF_GUIDE_NAMES:      # step()'s guides may be passed as they are: color_std is not read
+            continue
+        _check_host_buffer(buf, n)
+        setattr(f, name, buf.ctypes.data)
+    L.check(L.lib().lrt_svgf_filter_host(
+        ctypes.byref(d), color.ctypes.data_as(ctypes.c_void_p), moment2.ctypes.data_as(ctypes.c_void_p),
+        ctypes.byref(f) if guides else None, out.ctypes.data_as(ctypes.c_void_p),
+        variance_out.ctypes.data_as(ctypes.c_void_p) if variance_out is not None else None))
+    return out
+
+
+def svgf_filter_tensor(color, moment2, guides: Optional[dict], out=None, variance_out=None, stream=None, **params):
+    """svgf_filter_host on cuda float32 tensors (lrt_svgf_filter_device): asynchronous on `stream`
+    (a torch.cuda.Stream, default: current) and ordered only against it. Returns out."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = svgf_desc(w, h, **params)
+    n = w * h * 4
+    if not getattr(color, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color.device)
+
+    def ok(t):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == torch.float32
+                and t.is_contiguous() and t.numel() >= n)
+
+    if out is None:
+        with torch.cuda.stream(s):
+            out = color.clone()
+    for what, t in (("color", color), ("moment2", moment2), ("out", out), ("variance_out", variance_out)):
+        if not (ok(t) or (t is None and what == "variance_out")):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda float32 tensor of >= {n} elements")
+    unknown = [k for k in (guides or {}) if k not in L.FEATURE_NAMES]
+    if unknown:
+        raise L.LrtError(L.LRT_E_INVALID, f"unknown guide {unknown[0]!r}")
+    f = _tensor_features({k: v for k, v in (guides or {}).items() if k in L.SVGF_GUIDE_NAMES}, n,
+                         L.SVGF_GUIDE_NAMES, color.device)     # (step()'s color_std is not read)
+    L.check(L.lib().lrt_svgf_filter_device(
+        ctypes.byref(d), ctypes.c_void_p(color.data_ptr()), ctypes.c_void_p(moment2.data_ptr()),
+        ctypes.byref(f) if guides else None, ctypes.c_void_p(out.data_ptr()),
+        ctypes.c_void_p(variance_out.data_ptr()) if variance_out is not None else None,
+        ctypes.c_void_p(s.cuda_stream)))
+    return out
+
 
 def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
     """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
