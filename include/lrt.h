@@ -514,6 +514,95 @@ int lrt_svgf_filter_device(const lrt_svgf_desc* desc, const float* d_color, cons
 int lrt_svgf_filter_host(const lrt_svgf_desc* desc, const float* color, const float* moment2,
                          const lrt_features* guides, float* out, float* variance_out);
 
+/* ---- auto-exposure metering and tone mapping ------------------------------------- */
+
+/* The stage between the filters and the screen: meter the frame's exposure from the frame
+ * itself, adapt it over time, apply a tone curve, and quantise as lrt_present_bgra8 does. The
+ * frame is `height` rows of `width` RGBA float quads; alphas are never read.
+ *
+ * Metering (auto_exposure = 1). Per pixel, in f32, Y = 0.2126 R + 0.7152 G + 0.0722 B of the
+ * rgb as read. Its bin comes from the bits of Y, with no logarithm:
+ *     2^-16 <= Y < 2^16:        bin (bits(Y) >> 20) - 888: eight bins per octave, 256 bins
+ *     Y >= 2^16, +Inf included: `over`
+ *     everything else (zero, negative, NaN, below 2^-16): `under`
+ * The histogram is LRT_TONEMAP_HIST_WORDS counts h: the 256 bins, then `under`, then `over`
+ * (they sum to width * height). Bin b stands for the log2 luminance
+ *     l_b = (b >> 3) - 16 + log2(1 + ((b & 7) + 0.5) / 8)
+ * With N = the sum of the 256 bins and c_b their exclusive prefix sum, the percentile window
+ * takes m_b = max(0, min(c_b + h_b, p_high N) - max(c_b, p_low N)) from bin b (a firefly is a
+ * few pixels at the top of the histogram: p_high < 1 leaves them out, whatever their value), and
+ *     mean   = sum_b m_b l_b / sum_b m_b
+ *     target = clamp(log2(key) - mean + ev_bias, ev_min, ev_max)
+ * The state (read and written by the call; zero-filled = no history), with N > 0:
+ *     log2_exposure  = prev.frames >= 1 ? prev.log2_exposure + adapt (target - prev.log2_exposure)
+ *                                       : target           (adaptation is linear in log space)
+ *     log2_luminance = mean, counted = N / (width height), frames = prev.frames + 1
+ * and with N = 0: log2_exposure stays if prev.frames >= 1, else it is clamp(ev_bias, ev_min,
+ * ev_max); log2_luminance stays; counted = 0; frames = prev.frames + 1.
+ *
+ * Mapping. e = exp2(log2_exposure) of the state just written; with auto_exposure = 0 it is
+ * exp2(ev_bias), unclamped, and the state and the histogram are neither read nor written. Per
+ * channel c = x e, then c = c > 0 ? min(c, LRT_TM_MAX) : 0 (a NaN becomes 0), then
+ *     LRT_TM_LINEAR:   t = c
+ *     LRT_TM_REINHARD: t = c (1 + c / white^2) / (1 + c)          (white maps to 1)
+ *     LRT_TM_ACES:     t = clamp(c (2.51 c + 0.03) / (c (2.43 c + 0.59) + 0.14), 0, 1)
+ *                      (Narkowicz's fit of the ACES filmic curve)
+ * out.rgb = t (linear; its alpha stays); bgra = lrt_present_bgra8's quantiser applied to t.
+ *
+ * The metering is exact integer counting (deterministic); the state and the mapped frame are
+ * tolerance-checked against the NumPy restatement (tests/tonemap_ref.py), the quantiser of bgra
+ * is lrt_present_bgra8's bit for bit. */
+#define LRT_TONEMAP_BINS 256
+#define LRT_TONEMAP_HIST_WORDS 258          /* 256 bins, then `under`, then `over` */
+#define LRT_TM_LINEAR 0
+#define LRT_TM_REINHARD 1
+#define LRT_TM_ACES 2
+#define LRT_TM_MAX 65504.0f
+
+typedef struct lrt_tonemap_desc {
+    int32_t width, height;       /* a whole frame of RGBA float quads */
+    int32_t op;                  /* LRT_TM_* */
+    int32_t auto_exposure;       /* 0: log2 exposure = ev_bias; 1: metered */
+    int32_t flags, reserved;     /* 0 */
+    float key;                   /* > 0 */
+    float p_low, p_high;         /* 0 <= p_low < p_high <= 1 */
+    float ev_bias;               /* finite */
+    float ev_min, ev_max;        /* finite, ev_min <= ev_max */
+    float adapt;                 /* in (0, 1] */
+    float white;                 /* > 0 (Reinhard's white point) */
+} lrt_tonemap_desc;
+
+typedef struct lrt_exposure_state { float log2_exposure, log2_luminance, counted, frames; } lrt_exposure_state;
+
+/* The defaults for a width x height frame: ACES, auto_exposure 1, key 0.18, p_low 0.1,
+ * p_high 0.9, ev_bias 0, ev_min -8, ev_max 8, adapt 1, white 4. They are choices (the usual
+ * middle grey, a window that drops a tenth of the pixels at each end, no smoothing), not values
+ * tuned on this renderer's frames. */
+int lrt_tonemap_default(int width, int height, lrt_tonemap_desc* out);
+
+/* Meter and map d_color (device buffers). d_state: the exposure state, required with
+ * auto_exposure = 1. d_histogram: if given, receives the LRT_TONEMAP_HIST_WORDS counts (with
+ * auto_exposure = 1). d_out: if given, receives t in its rgb (12 B per pixel; its alpha stays);
+ * it may be d_color (in place). d_bgra: if given, receives the quantised pixels, width * height
+ * words. Both may be NULL with auto_exposure = 1: a meter-only call. With auto_exposure = 0,
+ * d_state and d_histogram may be NULL and are left untouched if given.
+ *
+ * LRT_E_INVALID, before any device use: NULL desc or color; sizes < 1 or width * height >
+ * INT_MAX / 4; an unknown op; auto_exposure outside 0..1; flags or reserved != 0; a parameter
+ * outside the range in the struct's comments, or not finite; auto_exposure = 1 without d_state;
+ * no output and no metering; d_bgra, d_histogram or d_state overlapping any other buffer (address
+ * ranges); d_out overlapping d_color other than being equal to it. Then LRT_E_STATE without
+ * lrt_initialize(). Asynchronous on `stream` and ordered only against it, with no host round
+ * trip (the exposure goes from the metering to the mapping through device memory); the
+ * intermediates live in that stream's scratch of the library. Acts on the first device. */
+int lrt_tonemap_device(const lrt_tonemap_desc* desc, const float* d_color, lrt_exposure_state* d_state,
+                       uint32_t* d_histogram, float* d_out, uint32_t* d_bgra, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_tonemap_device's bit for bit. */
+int lrt_tonemap_host(const lrt_tonemap_desc* desc, const float* color, lrt_exposure_state* state,
+                     uint32_t* histogram, float* out, uint32_t* bgra);
+
 #ifdef __cplusplus
 }
 #endif

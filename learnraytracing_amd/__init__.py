@@ -8,11 +8,12 @@ liblrt_hip.so only (no CPU fallback).
 """
 from ._lib import LrtError, lib  # noqa: F401
 from .renderer import (DrawTest, InitializeDevices, InitializeTest, Job, ShutdownTest,  # noqa: F401
-                       TemporalAccumulator, default_camera, denoise_desc, denoise_host, denoise_tensor, device_count, make_camera,
+                       TemporalAccumulator, ToneMapper, default_camera, denoise_desc, denoise_host, denoise_tensor, device_count, make_camera,
                        pinned_backbuffer, get_scene, render_device, render_host, render_host_features,
                        render_tensor, render_tensor_features, render_tensor_to_frame, set_scene, shard_rows,
                        svgf_desc, svgf_filter_host, svgf_filter_tensor,
-                       temporal_accumulate_host, temporal_accumulate_tensor, temporal_desc)
+                       temporal_accumulate_host, temporal_accumulate_tensor, temporal_desc,
+                       tonemap_desc, tonemap_host, tonemap_tensor)
 from .scene import default_scene, random_scene  # noqa: F401
 
 __version__ = "0.4.0"

@@ -132,6 +132,28 @@ class SvgfDesc(ctypes.Structure):             # lrt_svgf_desc
                 ("sigma_pos", ctypes.c_float), ("albedo_floor", ctypes.c_float)]
 
 
+TONEMAP_BINS = 256
+TONEMAP_HIST_WORDS = 258                      # 256 bins, then `under`, then `over`
+TM_LINEAR, TM_REINHARD, TM_ACES = 0, 1, 2
+TM_MAX = 65504.0
+TONEMAP_PARAMS = ("op", "auto_exposure", "key", "p_low", "p_high", "ev_bias", "ev_min", "ev_max", "adapt", "white")
+TONEMAP_OPS = {"linear": TM_LINEAR, "reinhard": TM_REINHARD, "aces": TM_ACES}
+
+
+class TonemapDesc(ctypes.Structure):          # lrt_tonemap_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("op", ctypes.c_int32), ("auto_exposure", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("key", ctypes.c_float), ("p_low", ctypes.c_float), ("p_high", ctypes.c_float),
+                ("ev_bias", ctypes.c_float), ("ev_min", ctypes.c_float), ("ev_max", ctypes.c_float),
+                ("adapt", ctypes.c_float), ("white", ctypes.c_float)]
+
+
+class ExposureState(ctypes.Structure):        # lrt_exposure_state
+    _fields_ = [("log2_exposure", ctypes.c_float), ("log2_luminance", ctypes.c_float),
+                ("counted", ctypes.c_float), ("frames", ctypes.c_float)]
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -181,6 +203,9 @@ SIGNATURES = {
     "lrt_svgf_default": (_i, [_i, _i, _c.POINTER(SvgfDesc)]),
     "lrt_svgf_filter_device": (_i, [_c.POINTER(SvgfDesc), _vp, _vp, _c.POINTER(Features), _vp, _vp, _vp]),
     "lrt_svgf_filter_host": (_i, [_c.POINTER(SvgfDesc), _vp, _vp, _c.POINTER(Features), _vp, _vp]),
+    "lrt_tonemap_default": (_i, [_i, _i, _c.POINTER(TonemapDesc)]),
+    "lrt_tonemap_device": (_i, [_c.POINTER(TonemapDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lrt_tonemap_host": (_i, [_c.POINTER(TonemapDesc), _vp, _vp, _vp, _vp, _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

@@ -1,6 +1,7 @@
 // Frame assembly after a gather (unshard, the RGB-only exchange) and the present step
 // (LinearToSRGB + BGRA8, main.cpp:109-141).
 #include "lrt_internal.h"
+#include "lrt_srgb.h"
 
 namespace lrt {
 
@@ -42,14 +43,7 @@ __global__ void unshard_rgb_kernel(const float* __restrict__ src, float4* __rest
     d[2] = sp[2];
 }
 
-// LinearToSRGB + pack (main.cpp:109-141): b | g << 8 | r << 16 per pixel.
-LRT_DEV uint32_t linear_to_srgb(float x) {   // main.cpp:109-115
-    x = (x < 0.0f) ? 0.0f : x;                                   // std::max(x, 0.0f)
-    x = 1.055f * libm::powf(x, 0.416666667f) - 0.055f;
-    x = (x < 0.0f) ? 0.0f : x;                                   // std::max(..., 0.0f)
-    uint32_t u = (uint32_t)(x * 255.9f);
-    return u < 255u ? u : 255u;                                  // std::min(u, 255u)
-}
+// LinearToSRGB (lrt_srgb.h) + pack (main.cpp:109-141): b | g << 8 | r << 16 per pixel.
 __global__ void present_kernel(const float4* __restrict__ src, uint32_t* __restrict__ dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

@@ -8,10 +8,11 @@
 //   lrt_order.hip     the pool kernel's tile-order cache and cost probe
 //   lrt_hostpath.hip  host backbuffers: DrawTest's pipelined path, its look-ahead, staging
 //   lrt_multi.hip     one process, several devices: split, RCCL gather, IPC frames
-//   lrt_frame.hip     frame assembly and present kernels
+//   lrt_frame.hip     frame assembly and present kernels (the quantiser itself: lrt_srgb.h)
 //   lrt_denoise.hip   the feature-guided a-trous denoiser (lrt_denoise_*): kernel and entry points
 //   lrt_temporal.hip  temporal reprojection and accumulation (lrt_temporal_*): kernel and entry points
 //   lrt_svgf.hip      the variance-guided filter over the temporal state (lrt_svgf_*): kernels and entry points
+//   lrt_tonemap.hip   auto-exposure metering and tone mapping (lrt_tonemap_*): kernels and entry points
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
 #pragma once

@@ -635,6 +635,133 @@ def svgf_filter_tensor(color, moment2, guides: Optional[dict], out=None, varianc
     return out
 
 
+# ---- auto-exposure metering and tone mapping -------------------------------------------------
+def tonemap_desc(width: int, height: int, **params) -> L.TonemapDesc:
+    """lrt_tonemap_default for a width x height frame, with any of op (an LRT_TM_* value or
+    "linear" / "reinhard" / "aces"), auto_exposure, key, p_low, p_high, ev_bias, ev_min, ev_max,
+    adapt, white overridden."""
+    d = L.TonemapDesc()
+    L.check(L.lib().lrt_tonemap_default(int(width), int(height), ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.TONEMAP_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown tonemap parameter {name!r}")
+        if name == "op" and isinstance(v, str):
+            if v not in L.TONEMAP_OPS:
+                raise L.LrtError(L.LRT_E_INVALID, f"unknown tone operator {v!r}")
+            v = L.TONEMAP_OPS[v]
+        setattr(d, name, int(v) if name in ("op", "auto_exposure") else float(v))
+    return d
+
+
+def _check_host_words(buf, n: int, what: str) -> None:
+    if not (isinstance(buf, np.ndarray) and buf.dtype in (np.uint32, np.int32) and buf.flags.c_contiguous
+            and buf.size >= n):
+        raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous uint32 array of >= {n} elements")
+
+
+def tonemap_host(color: np.ndarray, state: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None,
+                 bgra: Optional[np.ndarray] = None, histogram: Optional[np.ndarray] = None, **params):
+    """Meter and tone-map a frame on host buffers (lrt_tonemap_host). color: float32 [height, width,
+    4] (or flat with width=, height=). state: the exposure state, float32[4] (log2_exposure,
+    log2_luminance, counted, frames), read and updated in place; None: a new zeroed one (no
+    history). out: if given, receives the mapped linear rgb (its alpha stays; it may be color).
+    bgra: if given, uint32 of >= width * height, receives the quantised pixels. histogram: if
+    given, uint32 of >= 258, receives the counts. params: op, auto_exposure, key, p_low, p_high,
+    ev_bias, ev_min, ev_max, adapt, white. Returns the state (None with auto_exposure=0 and no state
+    given; it is left untouched then)."""
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = tonemap_desc(w, h, **params)
+    n = w * h * 4
+    _check_host_buffer(color, n)
+    if state is None and d.auto_exposure:
+        state = np.zeros(4, np.float32)
+    if state is not None:
+        _check_host_buffer(state, 4)
+    if out is not None:
+        _check_host_buffer(out, n)
+    if bgra is not None:
+        _check_host_words(bgra, w * h, "bgra")
+    if histogram is not None:
+        _check_host_words(histogram, L.TONEMAP_HIST_WORDS, "histogram")
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
+    L.check(L.lib().lrt_tonemap_host(ctypes.byref(d), ptr(color), ptr(state), ptr(histogram), ptr(out), ptr(bgra)))
+    return state
+
+
+def tonemap_tensor(color, state=None, out=None, bgra=None, histogram=None, stream=None, **params):
+    """tonemap_host on cuda tensors (lrt_tonemap_device): asynchronous on `stream` (a
+    torch.cuda.Stream, default: current) and ordered only against it; the exposure never visits
+    the host. color, out: float32; state: float32 of >= 4; bgra, histogram: int32 (or uint32).
+    Returns the state tensor."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = tonemap_desc(w, h, **params)
+    n = w * h * 4
+    if not getattr(color, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color.device)
+    words = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
+
+    def ok(t, dtypes, count):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype in dtypes
+                and t.is_contiguous() and t.numel() >= count)
+
+    if state is None and d.auto_exposure:
+        with torch.cuda.stream(s):
+            state = torch.zeros(4, device=color.device)
+    for what, t, dtypes, count in (("color", color, (torch.float32,), n), ("state", state, (torch.float32,), 4),
+                                   ("out", out, (torch.float32,), n), ("bgra", bgra, words, w * h),
+                                   ("histogram", histogram, words, L.TONEMAP_HIST_WORDS)):
+        if not (ok(t, dtypes, count) or (t is None and what != "color")):
+            kind = "float32" if dtypes == (torch.float32,) else "int32"
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {kind} tensor of >= {count} elements")
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    L.check(L.lib().lrt_tonemap_device(ctypes.byref(d), ptr(color), ptr(state), ptr(histogram), ptr(out), ptr(bgra),
+                                       ctypes.c_void_p(s.cuda_stream)))
+    return state
+
+
+class ToneMapper:
+    """The exposure state (16 B) and a histogram of a width x height frame on `device`: step() meters
+    a frame, adapts the exposure and maps the frame, all on the stream."""
+
+    def __init__(self, width: int, height: int, device="cuda:0"):
+        import torch
+
+        self.width, self.height = int(width), int(height)
+        if self.width < 1 or self.height < 1:
+            raise L.LrtError(L.LRT_E_INVALID, "invalid image size")
+        self.device = torch.device(device)
+        self._state = torch.zeros(4, device=self.device)
+        self.histogram = torch.zeros(L.TONEMAP_HIST_WORDS, dtype=torch.int32, device=self.device)
+
+    def reset(self, stream=None) -> None:
+        """Drop the exposure history (a new scene, a cut): the next step takes its target at once."""
+        import torch
+
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            self._state.zero_()
+
+    def step(self, color, bgra=None, out=None, stream=None, **params):
+        """One tonemap_tensor call of `color` against the mapper's state and histogram. Returns
+        (bgra, out) as given."""
+        tonemap_tensor(color, self._state, out=out, bgra=bgra, histogram=self.histogram, stream=stream,
+                       width=self.width, height=self.height, **params)
+        return bgra, out
+
+    @property
+    def state(self) -> dict:
+        """The four floats of the exposure state after the work enqueued so far (synchronises)."""
+        import torch
+
+        torch.cuda.synchronize(self.device)   # whichever streams the steps went to
+        v = self._state.cpu().tolist()
+        return dict(zip(("log2_exposure", "log2_luminance", "counted", "frames"), v))
+
+
 def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
     """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
     import torch
