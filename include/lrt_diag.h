@@ -12,7 +12,10 @@ extern "C" {
 /* ---- diagnostics (libm restatement, lrt_libm.h) --------------------------- */
 /* kind 0: sinf, 1: cosf, 2: powf(x, 5), 3: powf(x, 0.416666667f) (LinearToSRGB),
  * 4: sqrtf, 5: 1.0f / x (the device evaluates the path's short correctly rounded sequences),
- * 6 / 7: the sine / cosine results of the path's sincosf (one shared reduction).
+ * 6 / 7: the sine / cosine results of the path's sincosf (one shared reduction),
+ * 8: 1.0f / sqrtf(x) as normalize takes it (one range check for both steps), 9: the same
+ * from the two checked sequences of kinds 4 and 5, 10: kind 4's sequence without its range
+ * check (equal to kind 4 for x >= 2^-96, the closest-hit roots' proven operand range).
  * Host evaluation of the restatement. */
 int lrt_libm_eval_host(int kind, const float* in, float* out, long long n);
 /* Device evaluation of the same restatement (device pointers, blocking). */

@@ -12,6 +12,10 @@ LRT_HD float libm_eval(int kind, float x) {
         libm::sincosf(x, &sn, &cs);
         return kind == 6 ? sn : cs;
     }
+    // the forms with their range checks merged or dropped (lrt_trace.h), beside what they replace
+    if (kind == 8) return rsqrt_len(x);           // normalize's factor, one check for both steps
+    if (kind == 9) return rcp_rn(sqrt_rn(x));     // ... and the checked pair it stands for
+    if (kind == 10) return sqrt_fast(x);          // the fast root alone (SphereRoots' unchecked form)
     return kind == 0   ? libm::sinf(x)
            : kind == 1 ? libm::cosf(x)
            : kind == 2 ? libm::powf5(x)
@@ -430,14 +434,14 @@ int lrt_accel_eval(const lrt_sphere* spheres, int count, const float* rays, int 
 }
 
 int lrt_libm_eval_host(int kind, const float* in, float* out, long long n) {
-    if (kind < 0 || kind > 7 || !in || !out || n < 0) return fail(LRT_E_INVALID, "invalid libm eval arguments");
+    if (kind < 0 || kind > 10 || !in || !out || n < 0) return fail(LRT_E_INVALID, "invalid libm eval arguments");
     for (long long i = 0; i < n; ++i)
         out[i] = libm_eval(kind, in[i]);
     return LRT_OK;
 }
 
 int lrt_libm_eval_device(int kind, const float* d_in, float* d_out, long long n) {
-    if (kind < 0 || kind > 7 || !d_in || !d_out || n < 0) return fail(LRT_E_INVALID, "invalid libm eval arguments");
+    if (kind < 0 || kind > 10 || !d_in || !d_out || n < 0) return fail(LRT_E_INVALID, "invalid libm eval arguments");
     if (n == 0) return LRT_OK;
     libm_kernel<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(kind, d_in, d_out, n);
     LRT_HIP(hipGetLastError());

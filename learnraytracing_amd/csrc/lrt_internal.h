@@ -71,14 +71,17 @@ constexpr int kWavesPerEU = 4;
 constexpr int kPoolSamples = 4096;
 
 struct KernelArgs {
+    // What a path start reads, contiguous (the pool kernel's refill reads it in one batch of
+    // scalar loads, lrt_pool.h): the camera, the window and the row map.
     CameraDev cam;
+    int x0, xc, y0, rows;
+    int rb, rp, rph;
+    int rowIdent;   // the row map is the identity (rp == 1: local row ly is global row y0 + ly, any rb)
     const float4* sph;
     const float4* mats;
     const int* lights;
     int count, nlights;
     int width, height;
-    int x0, xc, y0, rows;
-    int rb, rp, rph;
     int frame0, frames, maxDepth;
     float4* out;
     unsigned long long* rays;
@@ -206,6 +209,10 @@ struct Context {
     unsigned long long order_tick = 0;
     hipStream_t stream = nullptr;
     int count = 0, nlights = 0;
+    // every sphere's packed r*r is a float >= 2^-70: the closest-hit roots' operand then never
+    // leaves the fast sqrt's range (SphereRoots), and the pool kernel's unchecked
+    // instance may be launched (upload_scene)
+    bool roots_in_range = false;
     float4* d_sph = nullptr;
     float4* d_mats = nullptr;
     int* d_lights = nullptr;

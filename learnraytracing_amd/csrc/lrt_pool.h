@@ -85,10 +85,15 @@ constexpr int kPoolGridWaves = 16;
 template <int kW>
 constexpr int pool_stack_bytes() { return 64 * kTraceLdsLevels * (kW > 1 ? 14 : 16); }
 
-template <int MAXD, bool kLds, int kAcc, int kPix, int kNS = 0, int kW = 1>
+// kNL > 0: the scene has exactly kNL lights (ScatterDir); kChk = false: the closest-hit scan's
+// roots skip their range check (SphereRoots; the host proves the scene's radii allow it). Both are
+// taken together, by the depth-8 fixed-scene instance of the reference's own scene shape (9
+// spheres, one light), when launch_pool finds them to hold.
+template <int MAXD, bool kLds, int kAcc, int kPix, int kNS = 0, int kW = 1, int kNL = 0, bool kChk = true>
 __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
     const KernelArgs a) {
     static_assert(kNS == 0 || (kLds && !kAcc), "a fixed sphere count is for the LDS linear scan");
+    static_assert((kNL == 0 && kChk) || kNS > 0, "a fixed light count and unchecked roots: fixed-scene instances");
     static_assert(kW == 1 || (kAcc == kAccGrid && !kLds), "multi-wave blocks: the grid instance");
     constexpr int kLv = kTraceLdsLevels;   // recursion stack levels in LDS
     constexpr bool kPacked = kW > 1;        // (pool_stack_bytes)
@@ -317,16 +322,26 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
                         if (k < N) {
                             const int j = k & ((1 << lgP) - 1), f = fr0 + (k >> lgP);
                             const int lx = tx0 + (j & ((1 << lgW) - 1)), ly = ty0 + (j >> lgW);
-                            const KArgPtr pa = opaque_args();   // window and camera, read here
-                            if (lx < pa->xc && ly < pa->rows) {   // TraceRowJob's per-pixel body (:270-279)
+                            // What a path start reads from the kernel arguments (window, row map,
+                            // camera: contiguous in KernelArgs), asked for in one batch of scalar
+                            // loads: one wait, where a read per dependent test made five. (Asked
+                            // ahead of the fold instead, the 30 scalars held across it cost the
+                            // general instances scratch and gained the trimmed one nothing,
+                            // profiles/r7_trim.)
+                            const KArgPtr pa = opaque_args();
+                            const int wx0 = pa->x0, wxc = pa->xc, wy0 = pa->y0, wrows = pa->rows;
+                            const int rb = pa->rb, rp = pa->rp, rph = pa->rph, rowIdent = pa->rowIdent;
+                            const CameraDev cam = pa->cam;
+                            if (lx < wxc && ly < wrows) {   // TraceRowJob's per-pixel body (:270-279)
                                 sec_count(sc, kSecCamera);
-                                const int x = pa->x0 + lx;
-                                const int rb = pa->rb;
-                                const int y = pa->y0 + (ly / rb) * rb * pa->rp + pa->rph * rb + ly % rb;
+                                const int x = wx0 + lx;
+                                // GlobalRow; an unsharded window's row map is the identity, and the
+                                // (wave-uniform) flag spares it the division
+                                int y = wy0 + ly;
+                                if (!rowIdent) y = wy0 + (ly / rb) * rb * rp + rph * rb + ly % rb;
                                 rng = PixelSeed((uint32_t)x, (uint32_t)y, (uint32_t)f);
                                 const float u = ((float)x + RandomFloat01(rng)) * invWidth;    // :272
                                 const float v = ((float)y + RandomFloat01(rng)) * invHeight;   // :273
-                                const CameraDev cam = pa->cam;
                                 r = GetRay(cam, u, v, rng, sc.rnlut);
                                 depth = 0;
                                 prevLambert = false;
@@ -386,7 +401,7 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
                         }
                     } else {
                         int sid;
-                        DualClosestHit<kNS>(r.orig, r.dir, hasS, dl.l, sc, nid, nt, sid);
+                        DualClosestHit<kNS, kChk>(r.orig, r.dir, hasS, dl.l, sc, nid, nt, sid);
                         lit = hasS && sid == dl.li;
                     }
                     if (pend) {   // the scatter event that produced r (:214), with its light if reached
@@ -416,7 +431,7 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
                         F3 lightE;
                         dl.on = false;
                         if constexpr (kAcc == kAccGrid) sc.gv = pool_grid_view<kAcc, kW>(smem);   // other lights' shadow rays
-                        const F3 X = ScatterDir<kAcc, kNS>(mat, nid, r, rec, lightE, rays, rng, sc, &dl, coherent);
+                        const F3 X = ScatterDir<kAcc, kNS, kNL>(mat, nid, r, rec, lightE, rays, rng, sc, &dl, coherent);
                         sec_count(sc, kSecPost);
                         const F3 dir = renormalize(normalize(X), sc.rnlut);   // Ray(rec.pos, normalize(X))
                         if ((mat.type != 1) | (dot(dir, rec.normal) > 0.0f)) {    // Metal absorbs (:147)
@@ -486,8 +501,11 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
                     acc.z = c3.z;
                     *mpx = acc;   // alpha as read
                     if (frame) {   // the exchange, fused: the pixel at its global row (GlobalRow)
-                        const int rb = pa->rb;
-                        const int gy = pa->y0 + (my / rb) * rb * pa->rp + pa->rph * rb + my % rb;
+                        int gy = pa->y0 + my;
+                        if (!pa->rowIdent) {
+                            const int rb = pa->rb;
+                            gy = pa->y0 + (my / rb) * rb * pa->rp + pa->rph * rb + my % rb;
+                        }
                         frame[(size_t)gy * pa->width + pa->x0 + mx] = acc;
                     }
                 }

@@ -62,7 +62,14 @@ int launch_pool(KernelArgs a, bool lds, int xc, int rows, hipStream_t s) {
     a.grid_lds_offset = wpb > 1 ? (int)(stack + (bstk + 15) / 16 * 16) : 0;
     const size_t ldsb = wpb > 1 ? stack + (bstk + 15) / 16 * 16 + grid_b : stack + scene + bstk;
     const bool fixed = lds && acc == kAccScan && a.count == kFixedSpheres;
-    const void* kern = acc == kAccGrid ? (lds ? (const void*)pool_kernel<MAXD, true, kAccGrid, kPix>
+    // the fixed-scene instance trimmed to one light and unchecked roots (pool_kernel's kNL, kChk):
+    // depth <= 8 only, and only for a scene that has one light and radii in the proven range
+    // (upload_scene); every other scene keeps the general instances
+    constexpr bool kTrimmed = MAXD <= 8;
+    const bool trim = kTrimmed && fixed && a.nlights == 1 && ctx().roots_in_range;
+    const void* kern_trim = nullptr;
+    if constexpr (kTrimmed) kern_trim = (const void*)pool_kernel<MAXD, true, kAccScan, kPix, kFixedSpheres, 1, 1, false>;
+    const void* kern = trim ? kern_trim : acc == kAccGrid ? (lds ? (const void*)pool_kernel<MAXD, true, kAccGrid, kPix>
                                           : wpb > 1 ? (const void*)pool_kernel<MAXD, false, kAccGrid, kPix, 0, kW>
                                               : (const void*)pool_kernel<MAXD, false, kAccGrid, kPix>)
                        : acc == kAccBvh ? (lds ? (const void*)pool_kernel<MAXD, true, kAccBvh, kPix>
@@ -146,6 +153,8 @@ int launch_pool(KernelArgs a, bool lds, int xc, int rows, hipStream_t s) {
     } else if (acc == kAccBvh) {
         if (lds) pool_kernel<MAXD, true, kAccBvh, kPix><<<grid, 64, ldsb, s>>>(a);
         else pool_kernel<MAXD, false, kAccBvh, kPix><<<grid, 64, ldsb, s>>>(a);
+    } else if (trim) {
+        if constexpr (kTrimmed) pool_kernel<MAXD, true, kAccScan, kPix, kFixedSpheres, 1, 1, false><<<grid, 64, ldsb, s>>>(a);
     } else if (fixed) {
         pool_kernel<MAXD, true, kAccScan, kPix, kFixedSpheres><<<grid, 64, ldsb, s>>>(a);
     } else {
@@ -172,14 +181,16 @@ int launch_pool(KernelArgs a, bool lds, int xc, int rows, hipStream_t s) {
     for (auto* u : users)
         if (u)
             if (int rc = order_used(*u, s)) return rc;
+    // chk: the scan's roots carry their range check; nl: the instance's compile-time light count
+    // (0: the scene's own, at run time)
     // order: 0 queue order (tile order off), 1 recording in queue order, 2 the signature's own
     // sorted order, 3 recording with the order borrowed from the same geometry, 4 recording in
     // the probe's order, 5 the refining pass (recording in the first pass's sorted order)
     snprintf(g_last_launch, sizeof(g_last_launch),
              "kernel=pool_kernel maxd=%d lds=%d bvh=%d acc=%s pix=%d ns=%d grid=%u tasks=%lld order=%d per_cu=%d wpb=%d "
-             "split_from=%d",
+             "split_from=%d chk=%d nl=%d",
              MAXD, lds ? 1 : 0, acc == kAccBvh ? 1 : 0, acc_name(acc), kPix, fixed ? kFixedSpheres : 0, grid.x, ntiles,
-             !users[0] ? 0 : !record ? 2 : record == 2 ? 5 : probed ? 4 : users[1] ? 3 : 1, per_cu, wpb, a.splitFrom);
+             !users[0] ? 0 : !record ? 2 : record == 2 ? 5 : probed ? 4 : users[1] ? 3 : 1, per_cu, wpb, a.splitFrom, trim ? 0 : 1, trim ? 1 : 0);
 #ifdef LRT_EXP_SECSTATS
     secstats_dump(d_sec, s);
 #endif

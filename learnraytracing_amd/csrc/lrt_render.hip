@@ -387,6 +387,7 @@ int render_device(const lrt_render_desc* d, float* d_buf, unsigned long long* d_
     a.rb = d->row_block;
     a.rp = d->row_period;
     a.rph = d->row_phase;
+    a.rowIdent = d->row_period == 1 ? 1 : 0;   // (validate: row_phase < row_period, so 0 here)
     a.frame0 = d->frame0;
     a.frames = d->frames;
     a.maxDepth = d->max_depth;

@@ -480,6 +480,9 @@ int upload_scene(Context& c, const lrt_sphere* s, const lrt_material* m, int n) 
     c.count = n;
     ++c.scene_version;
     c.nlights = (int)lights.size();
+    // SphereRoots' precondition, on the r*r the kernels read (NaN fails the comparison)
+    c.roots_in_range = true;
+    for (const float4& q : sph) c.roots_in_range = c.roots_in_range && q.w >= 0x1p-70f;
     c.spheres.assign(s, s + n);
     c.mats.assign(m, m + n);
     return LRT_OK;

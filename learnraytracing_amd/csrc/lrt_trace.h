@@ -49,7 +49,10 @@ LRT_DEV F3 cross(F3 a, F3 b) {                                                  
 // Operands outside those ranges (or NaN) send the whole wave through the generic
 // sequence: a wave-uniform branch, essentially never taken. Host builds (the BVH
 // diagnostics) use the plain operations.
-LRT_DEV float sqrt_rn(float x) {
+// sqrt_fast / rcp_fast are the bare sequences, for call sites whose operand is proven to lie in
+// the fast range (the proof stands at each site, and in DESIGN §2); sqrt_rn / rcp_rn add the
+// range check and are what every other caller uses.
+LRT_DEV float sqrt_fast(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     float s = __builtin_amdgcn_sqrtf(x);
     const float sd = __int_as_float(__float_as_int(s) - 1);
@@ -58,28 +61,60 @@ LRT_DEV float sqrt_rn(float x) {
     const float ru = __builtin_fmaf(-su, s, x);
     s = rd <= 0.0f ? sd : s;
     s = ru > 0.0f ? su : s;
-    if (__builtin_expect(__ballot(!(x >= 0x1p-96f)) != 0, 0)) s = __builtin_sqrtf(x);
     return s;
 #else
     return __builtin_sqrtf(x);
 #endif
 }
-LRT_DEV float rcp_rn(float x) {
+LRT_DEV float rcp_fast(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     float r = __builtin_amdgcn_rcpf(x);
     float e = __builtin_fmaf(-x, r, 1.0f);
     r = __builtin_fmaf(e, r, r);
     e = __builtin_fmaf(-x, r, 1.0f);
     r = __builtin_fmaf(e, r, r);
-    const float ax = __builtin_fabsf(x);
-    if (__builtin_expect(__ballot(!(ax >= 0x1p-125f && ax <= 0x1p125f)) != 0, 0)) r = 1.0f / x;
     return r;
 #else
     return 1.0f / x;
 #endif
 }
+LRT_DEV float sqrt_rn(float x) {
+    float s = sqrt_fast(x);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_expect(__ballot(!(x >= 0x1p-96f)) != 0, 0)) s = __builtin_sqrtf(x);
+#endif
+    return s;
+}
+LRT_DEV float rcp_rn(float x) {
+    float r = rcp_fast(x);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float ax = __builtin_fabsf(x);
+    if (__builtin_expect(__ballot(!(ax >= 0x1p-125f && ax <= 0x1p125f)) != 0, 0)) r = 1.0f / x;
+#endif
+    return r;
+}
 LRT_DEV float length(F3 v) { return sqrt_rn(v.x * v.x + v.y * v.y + v.z * v.z); } // maths.h:15
-LRT_DEV F3 normalize(F3 v) { float k = rcp_rn(length(v)); return f3(v.x * k, v.y * k, v.z * k); } // maths.h:93
+// rcp_rn(sqrt_rn(d)), normalize's factor, with ONE range check for both steps: for a finite
+// d >= 2^-96 the root is the fast sequence's, and it lies in [2^-48, 2^64], inside rcp_rn's
+// [2^-125, 2^125], so neither of the two checks could fire. The test is one unsigned compare
+// of the bit pattern, f2u(d) - f2u(2^-96) <= f2u(FLT_MAX) - f2u(2^-96): zero, denormals and
+// smaller normals wrap around to large values, negatives (sign bit), infinity and NaN lie
+// above the span by themselves. A lane outside sends the wave through the checked pair, as
+// before.
+LRT_DEV float rsqrt_len(float d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float k = rcp_fast(sqrt_fast(d));
+    if (__builtin_expect(__ballot(libm::f2u(d) - 0x0f800000u > 0x7f7fffffu - 0x0f800000u) != 0, 0))
+        k = rcp_rn(sqrt_rn(d));
+    return k;
+#else
+    return 1.0f / __builtin_sqrtf(d);
+#endif
+}
+LRT_DEV F3 normalize(F3 v) {                                                        // maths.h:93
+    float k = rsqrt_len(v.x * v.x + v.y * v.y + v.z * v.z);   // length()'s sum, same order
+    return f3(v.x * k, v.y * k, v.z * k);
+}
 // normalize() of a vector that is already unit length to a few ulps (the reference
 // normalises twice: every Ray ctor normalises its direction again, maths.h:133-137).
 // Its |y|^2 lies within kRenormR ulps of 1, so 1/sqrt(|y|^2) comes from a table of
@@ -270,9 +305,17 @@ LRT_DEV void sec_count(const SceneView& sc, int sec) { sec_enter(sc, sec, true);
 // Inside, the reference's if / else-if is taken as selects over both roots, its && as bitwise
 // ands: each short-circuit was a divergent region of its own, whose exec bookkeeping (scalar
 // instructions, a branch) cost more than the second root's add (the grid walk: profiles/r4_y).
+// kChk = false (a scene whose every r*r >= 2^-70: Context::roots_in_range): the root's operand
+// -ifHit > 0, with ifHit = fl(fl(rr - p*p) - r2), is then never below 2^-94, so the fast sequence
+// applies without its range check. Write A = fl(rr - p*p) (any float; NaN makes ifHit NaN, which
+// fails ifHit < 0). If A <= r2 / 2 the exact difference r2 - A is at least r2 / 2 >= 2^-71, and
+// so is its rounding. Otherwise r2 / 2 < A < r2, A - r2 is exact (Sterbenz) and non-zero, and
+// both floats are at least 2^-71, hence multiples of 2^-94: so is their difference. (-ifHit =
+// +inf, from an overflowed p*p, takes the fast sequence with the check too.) DESIGN §2.
+template <bool kChk = true>
 LRT_DEV void SphereRoots(float rsProj, float ifHit, float tMin, float& closestT, int& id, int i) {
     if (ifHit < 0.0f) {
-        const float halfCut = sqrt_rn(-ifHit);
+        const float halfCut = kChk ? sqrt_rn(-ifHit) : sqrt_fast(-ifHit);
         const float t1 = rsProj - halfCut, t2 = rsProj + halfCut;
         const bool ok1 = (t1 > tMin) & (t1 < closestT);
         const bool ok2 = (t2 > tMin) & (t2 < closestT);
@@ -371,7 +414,9 @@ struct DeferredLight {
     int id;          // the scattering sphere (pool kernel: its stack entry's material)
 };
 
-template <int kAcc = 0, int kNS = 0>
+// kNL > 0: the scene has exactly kNL lights (the pool kernel's one-light instance: the loop is
+// its single deferred sample, and the undeferred shadow scan drops out).
+template <int kAcc = 0, int kNS = 0, int kNL = 0>
 LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit& rec, F3& outLightE,
                       int& inoutRayCount, uint32_t& rng, const SceneView& sc, DeferredLight* defer = nullptr,
                       bool coherent = false) {
@@ -381,11 +426,12 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
         // the first light's index and sphere, read before RandomUnitVector: their two dependent
         // LDS reads are in flight across it instead of waited for at the light loop's start
         // (config 2 -0.3 % / -0.7 % on two streams / one, config 3 -0.5 %: profiles/r6_ao)
-        const int i0 = sc.nlights > 0 ? sc.lights[0] : 0;
+        const int nlights = kNL > 0 ? kNL : sc.nlights;
+        const int i0 = nlights > 0 ? sc.lights[0] : 0;
         const float4 s0 = sc.sph[i0];
         F3 target = rec.pos + rec.normal + RandomUnitVector(rng);
         const F3 X = target - rec.pos;
-        for (int k = 0; k < sc.nlights; ++k) {
+        for (int k = 0; k < nlights; ++k) {
             int i = k == 0 ? i0 : sc.lights[k];
             if (i == matId) continue;  // :98
             float4 s = k == 0 ? s0 : sc.sph[i];
@@ -410,7 +456,7 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
             l = normalize_member(l);                                                      // :117
             float tLight;
             ++inoutRayCount;                                                              // :122
-            if (defer && k == sc.nlights - 1) {   // the last light: traced with the bounce ray
+            if (defer && k == nlights - 1) {   // the last light: traced with the bounce ray
                 float omega = 2.0f * kPI * (1.0f - cosAMax);
                 F3 rdir = r_in.dir;
                 F3 nl = dot(rec.normal, rdir) < 0.0f ? rec.normal : -rec.normal;
@@ -581,7 +627,7 @@ LRT_DEV F3 Trace(Ray r, int maxDepth, int& inoutRayCount, uint32_t& rng, const S
 // values HitSphere computes for each ray (maths.cpp:54-59) -- and each ray keeps its own
 // shrinking closestT exactly as HitWorld does, so both results are bit-identical to two
 // separate scans. Saves the shadow ray's separate, partly occupied pass.
-template <int kNS = 0>
+template <int kNS = 0, bool kChk = true>
 LRT_DEV void DualClosestHit(const F3& o, const F3& db, bool hasShadow, const F3& ds, const SceneView& sc,
                             int& idB, float& tB, int& idS) {
     float closestB = kMaxT, closestS = kMaxT;
@@ -593,12 +639,12 @@ LRT_DEV void DualClosestHit(const F3& o, const F3& db, bool hasShadow, const F3&
         {
             const float rsProj = dot(rs, db);
             const float ifHit = rr - rsProj * rsProj - s.w;
-            SphereRoots(rsProj, ifHit, kMinT, closestB, idB, i);
+            SphereRoots<kChk>(rsProj, ifHit, kMinT, closestB, idB, i);
         }
         if (hasShadow) {
             const float rsProj = dot(rs, ds);
             const float ifHit = rr - rsProj * rsProj - s.w;
-            SphereRoots(rsProj, ifHit, kMinT, closestS, idS, i);
+            SphereRoots<kChk>(rsProj, ifHit, kMinT, closestS, idS, i);
         }
     };
     if constexpr (kNS > 0) {
