@@ -4,7 +4,7 @@
 // standard deviation (as in SVGF). One launch per pass; pass k uses the 5x5 B3-spline taps at
 // dilation s = 2^k. Not bit-pinned (the reference has no such filter): contraction and the
 // hardware exp are allowed here, unlike in the render units.
-#include "lrt_internal.h"
+#include "lrt_atrous.h"
 
 #pragma clang fp contract(fast)
 
@@ -23,82 +23,41 @@ struct DenoiseArgs {
     int rgb_only;        // the last pass: 12 B stores, the destination's alpha stays
 };
 
-// The tiled form. A workgroup filters kTileW columns x kTileRows rows that lie s apart (one
-// residue class of the rows mod s), so that every tap of its pixels falls on the workgroup's own
-// lattice: the LDS tile holds the kTileRows + 4 lattice rows y0 + (r - 2) s and the
-// kTileW + 4 s contiguous columns x0 - 2 s .. x0 + kTileW + 2 s - 1 of the pass's input colour
-// and the three per-tap guides, alphas dropped: 12 floats per pixel as six float2 planes (a
-// wave's tap read is 64 consecutive float2 of one plane: ds_read_b64, no bank conflict). Every
-// global access is a contiguous run of float4 along a row. At s = 16 the tile is 8 x 128 pixels
-// = 48 KiB; 2.1 (s = 1) to 4 (s = 16) pixels are staged per pixel filtered, against 25 read
-// by the direct form.
-constexpr int kTileW = 64, kTileRows = 4, kTileLds = kTileRows + 4;
-constexpr int kPlanes = 6;
-inline int tile_width(int s) { return kTileW + 4 * s; }
-inline size_t tile_bytes(int s) { return sizeof(float2) * kPlanes * kTileLds * (size_t)tile_width(s); }
-
-// The taps are branch-free: pixels outside the image and absent guides are staged as zeros and
-// an out-of-image tap gets a zero spline weight; the guides are staged divided by their sigma
-// (times sqrt(log2 e), so that a tap's weight is one v_exp_f32 of its summed squares).
-// world_pos is staged relative to an anchor, the position at the workgroup's first pixel, as
-// fma(x, k, -(anchor k)): one rounding, of a value of the size of the tile's extent instead of
-// the scene's distance from the origin (x k alone: at 1000 units, sigma_pos 0.5, an ulp of the
-// staged value is 4e-4 of a sigma and the weights were off by 5e-5 of the result). The taps take
-// differences of staged values, in which the constant cancels, its own rounding included; a
-// non-finite component of the anchor counts as 0. No instruction more per staged pixel.
-// kStd: color_std is given (else there is no colour term).
+// A pass over the lattice tile of lrt_atrous.h, which explains the tile, the branch-free taps and
+// the anchor-relative world_pos. kStd: color_std is given (else there is no colour term).
 template <bool kStd>
 __global__ __launch_bounds__(kTileW* kTileRows) void denoise_kernel(DenoiseArgs a) {
     extern __shared__ float2 tile[];
     const int s = a.s, tw = kTileW + 4 * s;
     const int plane = kTileLds * tw;   // float2s per plane
     const int tx = threadIdx.x, ty = threadIdx.y;
-    // blockIdx.y = group * s + phase: the rows y0 + r s, r = 0 .. kTileRows - 1
-    const int x0 = blockIdx.x * kTileW;
-    const int y0 = (blockIdx.y / s) * (kTileRows * s) + blockIdx.y % s;
+    const int x0 = blockIdx.x * kTileW, y0 = tile_y0(s);
     if (y0 >= a.h) return;   // the whole workgroup: the last group's unused phases
     const float kn = a.kn, kx = a.kx, ka = a.ka;
-    const float4 an = a.pos[(size_t)y0 * a.w + x0];   // uniform over the workgroup, inside the image
-    auto finite_or_0 = [](const float v) { return fabsf(v) < INFINITY ? v : 0.0f; };   // (a NaN fails the compare)
-    const float ax = finite_or_0(-an.x * kx), ay = finite_or_0(-an.y * kx), az = finite_or_0(-an.z * kx);   // -(anchor k)
+    const float3 an = tile_anchor(a.pos, a.w, x0, y0, kx);   // uniform over the workgroup
     // the centre's std first: its latency passes behind the staging
     const int px = x0 + tx, py = y0 + ty * s;
     const bool live = px < a.w && py < a.h;
     float4 sd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (kStd && live) sd = a.std[(size_t)py * a.w + px];
-    // stage: a thread takes up to kStage tile pixels (lattice rows ty and ty + kTileRows, columns
-    // tx and tx + kTileW). Straight-line: every load is issued, from an address clamped into the
-    // image (and into the tile: the lanes past its width all read its last column), before the
-    // first LDS store waits for one; what lay outside becomes zero afterwards.
-    constexpr int kStage = 4;
-    static_assert(kTileLds == 2 * kTileRows, "two lattice rows per thread row");
-    static_assert(4 * (1 << (LRT_DENOISE_MAX_ITER - 1)) <= kTileW, "two columns per thread cover the tile");
-    float4 c[kStage], n[kStage], x[kStage], al[kStage];
-    bool ok[kStage];
+    // stage, straight-line: all of a thread's loads, then its LDS stores (tile_slot)
+    static_assert(tile_covers(LRT_DENOISE_MAX_ITER), "two columns per thread cover the tile");
+    float4 c[kTileStage], n[kTileStage], x[kTileStage], al[kTileStage];
+    bool ok[kTileStage];
 #pragma unroll
-    for (int u = 0; u < kStage; ++u) {
-        const int lr = ty + (u >> 1) * kTileRows, cx = min(tx + (u & 1) * kTileW, tw - 1);
-        const int gy = y0 + (lr - 2) * s, gx = x0 - 2 * s + cx;
-        ok[u] = gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
-        const size_t ig = (size_t)min(max(gy, 0), a.h - 1) * a.w + min(max(gx, 0), a.w - 1);
+    for (int u = 0; u < kTileStage; ++u) {
+        const size_t ig = tile_slot(u, tx, ty, x0, y0, s, tw, a.w, a.h, ok[u]);
         c[u] = a.in[ig];
         n[u] = a.nrm[ig];
         x[u] = a.pos[ig];
         al[u] = a.alb[ig];
     }
 #pragma unroll
-    for (int u = 0; u < kStage; ++u) {
-        const int lr = ty + (u >> 1) * kTileRows, cx = tx + (u & 1) * kTileW;
+    for (int u = 0; u < kTileStage; ++u) {
+        const int lr = tile_slot_row(u, ty), cx = tile_slot_col(u, tx);
         if (cx >= tw) continue;
         const bool on = ok[u] && a.nrm != a.in, ox = ok[u] && a.pos != a.in, oa = ok[u] && a.alb != a.in;
-        const float4 cc = c[u], nn = n[u], xx = x[u], aa = al[u];
-        float2* t = tile + lr * tw + cx;
-        t[0 * plane] = make_float2(ok[u] ? cc.x : 0.0f, ok[u] ? cc.y : 0.0f);
-        t[1 * plane] = make_float2(ok[u] ? cc.z : 0.0f, on ? nn.x * kn : 0.0f);
-        t[2 * plane] = make_float2(on ? nn.y * kn : 0.0f, on ? nn.z * kn : 0.0f);
-        t[3 * plane] = make_float2(ox ? fmaf(xx.x, kx, ax) : 0.0f, ox ? fmaf(xx.y, kx, ay) : 0.0f);
-        t[4 * plane] = make_float2(ox ? fmaf(xx.z, kx, az) : 0.0f, oa ? aa.x * ka : 0.0f);
-        t[5 * plane] = make_float2(oa ? aa.y * ka : 0.0f, oa ? aa.z * ka : 0.0f);
+        tile_store(tile + lr * tw + cx, plane, ok[u], on, ox, oa, c[u], n[u], x[u], al[u], kn, kx, an, ka);
     }
     float inv_c = 0.0f;
     if (kStd && live) {
@@ -107,13 +66,12 @@ __global__ __launch_bounds__(kTileW* kTileRows) void denoise_kernel(DenoiseArgs 
     __syncthreads();
     if (!live) return;
 
-    const float hw[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     float hx[5], hy[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         const int gx = px + (i - 2) * s, gy = py + (i - 2) * s;
-        hx[i] = gx >= 0 && gx < a.w ? hw[i] : 0.0f;
-        hy[i] = gy >= 0 && gy < a.h ? hw[i] : 0.0f;
+        hx[i] = tile_spline(i, gx, a.w);
+        hy[i] = tile_spline(i, gy, a.h);
     }
     const float2* ctr = tile + (ty + 2) * tw + tx + 2 * s;
     const float2 p0 = ctr[0 * plane], p1 = ctr[1 * plane], p2 = ctr[2 * plane];
@@ -133,13 +91,8 @@ __global__ __launch_bounds__(kTileW* kTileRows) void denoise_kernel(DenoiseArgs 
                 const float dx = p0.x - q0.x, dy = p0.y - q0.y, dz = p1.x - q1.x;
                 e = (dx * dx + dy * dy + dz * dz) * inv_c;
             }
+            e = tile_guide_dist(e, p1, p2, p3, p4, q1, q2, q3, q4);
             float d;
-            d = p1.y - q1.y, e += d * d;
-            d = p2.x - q2.x, e += d * d;
-            d = p2.y - q2.y, e += d * d;
-            d = p3.x - q3.x, e += d * d;
-            d = p3.y - q3.y, e += d * d;
-            d = p4.x - q4.x, e += d * d;
             d = p4.y - q4.y, e += d * d;
             d = p5.x - q5.x, e += d * d;
             d = p5.y - q5.y, e += d * d;
@@ -167,9 +120,7 @@ __global__ __launch_bounds__(kTileW* kTileRows) void denoise_kernel(DenoiseArgs 
 }
 
 static hipError_t launch_pass(DenoiseArgs a, hipStream_t s) {
-    const int groups = (a.h + kTileRows * a.s - 1) / (kTileRows * a.s);
-    const dim3 grid((unsigned)((a.w + kTileW - 1) / kTileW), (unsigned)(groups * a.s));
-    const dim3 block(kTileW, kTileRows);
+    const dim3 grid = tile_grid(a.w, a.h, a.s), block(kTileW, kTileRows);
     // an absent guide reads the colour instead (a valid address) and is staged as zeros
     if (!a.nrm) a.nrm = a.in;
     if (!a.pos) a.pos = a.in;
@@ -184,8 +135,7 @@ static hipError_t launch_pass(DenoiseArgs a, hipStream_t s) {
 static int validate_denoise(const lrt_denoise_desc* d, const float* color, const lrt_features* g, const float* out) {
     if (!d) return fail(LRT_E_INVALID, "desc is NULL");
     if (!color || !out) return fail(LRT_E_INVALID, "color or out is NULL");
-    if (d->width < 1 || d->height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    if ((long long)d->width * d->height > INT_MAX / 4) return fail(LRT_E_INVALID, "image too large");
+    if (int rc = validate_frame_size(d->width, d->height)) return rc;
     if (d->iterations < 1 || d->iterations > LRT_DENOISE_MAX_ITER)
         return fail(LRT_E_INVALID, "iterations must be in 1..LRT_DENOISE_MAX_ITER");
     if (d->flags != 0) return fail(LRT_E_INVALID, "flags must be 0");
@@ -207,8 +157,7 @@ static int denoise_device(const lrt_denoise_desc* d, const float* color, const l
     float4* tmp[2] = {nullptr, nullptr};
     if (ntmp) {
         void* p = nullptr;
-        if (const hipError_t e = stream_scratch(s, ntmp * npix * sizeof(float4), &p))
-            return e == hipErrorOutOfMemory ? fail(LRT_E_NOMEM, "denoise scratch") : hip_fail(e, "denoise scratch");
+        if (int rc = scratch_or_fail(s, ntmp * npix * sizeof(float4), "denoise scratch", &p)) return rc;
         tmp[0] = static_cast<float4*>(p);
         tmp[1] = ntmp == 2 ? tmp[0] + npix : nullptr;
     }
@@ -281,7 +230,7 @@ int lrt_denoise_device(const lrt_denoise_desc* desc, const float* d_color, const
     RoctxRange rr_("lrt_denoise_device");
     if (int rc = validate_denoise(desc, d_color, d_guides, d_out)) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_devs[0].ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);   // context 0's device (device 0 of lrt_initialize_devices)
     return denoise_device(desc, d_color, d_guides, d_out, (hipStream_t)stream);
 }
@@ -290,7 +239,7 @@ int lrt_denoise_host(const lrt_denoise_desc* desc, const float* color, const lrt
     RoctxRange rr_("lrt_denoise_host");
     if (int rc = validate_denoise(desc, color, guides, out)) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_devs[0].ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     const size_t bytes = (size_t)desc->width * desc->height * 4 * sizeof(float);
     hipStream_t s = ctx().stream;

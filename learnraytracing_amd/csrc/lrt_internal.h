@@ -13,8 +13,12 @@
 //   lrt_temporal.hip  temporal reprojection and accumulation (lrt_temporal_*): kernel and entry points
 //   lrt_svgf.hip      the variance-guided filter over the temporal state (lrt_svgf_*): kernels and entry points
 //   lrt_tonemap.hip   auto-exposure metering and tone mapping (lrt_tonemap_*): kernels and entry points
+//   lrt_atrous.h      the lattice tile of the two a-trous kernels (denoise, svgf): geometry, anchor, staging, taps
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
+// The host plumbing that the four post-process units (denoise, temporal, svgf, tonemap) share is
+// below: the size and aliasing checks, the staging allocation of a *_host call, the stream scratch
+// of a *_device call, the ready check.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -415,6 +419,36 @@ void wavetrace_dump(unsigned long long* d, size_t waves, hipStream_t s);
 unsigned long long* secstats_buffer(hipStream_t s);
 void secstats_dump(const unsigned long long* d_sec, hipStream_t s);
 #endif
+
+// ---- the post-process units (lrt_denoise, lrt_temporal, lrt_svgf, lrt_tonemap). The strings are
+// part of the ABI (lrt_last_error()).
+// A frame of width x height pixels whose float count fits an int.
+inline int validate_frame_size(int width, int height) {
+    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
+    if ((long long)width * height > INT_MAX / 4) return fail(LRT_E_INVALID, "image too large");
+    return LRT_OK;
+}
+// Do the byte ranges [p, p + bytes_p) and [q, q + bytes_q) share a byte? A null pointer: no.
+inline bool ranges_overlap(const void* p, size_t bytes_p, const void* q, size_t bytes_q) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + bytes_q && b < a + bytes_p;
+}
+// Context 0 is initialised (the caller holds g_mu).
+inline int require_initialized() {
+    return g_devs[0].ready ? LRT_OK : fail(LRT_E_STATE, "lrt_initialize() has not been called");
+}
+// One device allocation that lives for a *_host call: the mirrors of its buffers.
+template <class T>
+struct DeviceStaging {
+    T* p = nullptr;
+    ~DeviceStaging() { if (p) (void)hipFree(p); }
+};
+// At least `bytes` of stream s's scratch (stream_scratch), its failure as an lrt_* code.
+inline int scratch_or_fail(hipStream_t s, size_t bytes, const char* what, void** out) {
+    const hipError_t e = stream_scratch(s, bytes, out);
+    if (e == hipSuccess) return LRT_OK;
+    return e == hipErrorOutOfMemory ? fail(LRT_E_NOMEM, what) : hip_fail(e, what);
+}
 
 // ---- lrt_v0_d8.hip / lrt_v0_d64.hip: v0 launches for max_depth <= 8 / <= 64. colours: the
 // pipelined host path's colours-only render (one frame lane, sample planes)

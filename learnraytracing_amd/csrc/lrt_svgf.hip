@@ -5,7 +5,7 @@
 // together, the colour weight scaled by the 3x3 pre-filtered variance of the pass's own input.
 // Not bit-pinned (the reference has no such filter): contraction and the hardware exp are allowed
 // here, unlike in the render units.
-#include "lrt_internal.h"
+#include "lrt_atrous.h"
 
 #pragma clang fp contract(fast)
 
@@ -28,8 +28,6 @@ struct SvgfArgs {
     float min_history;
 };
 
-LRT_DEV float finite_or_0(const float v) { return fabsf(v) < INFINITY ? v : 0.0f; }   // (a NaN fails the compare)
-
 // The demodulation divisor of a pixel from its raw normal and albedo quads.
 LRT_DEV float3 divisor(const SvgfArgs& a, const float4 n4, const float4 a4) {
     const bool hit = !a.has_n || n4.x * n4.x + n4.y * n4.y + n4.z * n4.z >= 0.25f;
@@ -42,7 +40,7 @@ LRT_DEV float3 divisor(const SvgfArgs& a, const float4 n4, const float4 a4) {
 // that holds such a pixel (a workgroup-wide vote on the centres' n) stages its tile plus a halo
 // of 3 in LDS first -- colour, moment, normal and position, alphas dropped: 12 floats per pixel
 // as six float2 planes, the guides divided by their sigma and world_pos relative to the
-// workgroup's first pixel, exactly as the pass kernel stages them -- so that a first frame,
+// workgroup's first pixel (tile_anchor, as the pass kernel stages them) -- so that a first frame,
 // where every pixel takes that branch, reads 2.1 pixels per pixel from memory and its 49 taps
 // from LDS. A workgroup with history everywhere stages nothing.
 constexpr int k0W = 32, k0H = 8, k0R = 3;
@@ -63,8 +61,7 @@ __global__ __launch_bounds__(k0W* k0H) void svgf_stage0_kernel(SvgfArgs a) {
                            fmaxf(m4.z - c4.z * c4.z, 0.0f));
     if (__syncthreads_or(spatial)) {   // uniform over the workgroup
         const float kn = a.kn, kx = a.kx;
-        const float4 an = a.pos[(size_t)y0 * a.w + x0];   // inside the image
-        const float ax = finite_or_0(-an.x * kx), ay = finite_or_0(-an.y * kx), az = finite_or_0(-an.z * kx);
+        const float3 an = tile_anchor(a.pos, a.w, x0, y0, kx);
         // straight-line staging: every load is issued, from an address clamped into the image (and
         // into the tile), before the first LDS store waits for one
         float4 c[k0Stage], m[k0Stage], n[k0Stage], x[k0Stage];
@@ -88,8 +85,8 @@ __global__ __launch_bounds__(k0W* k0H) void svgf_stage0_kernel(SvgfArgs a) {
             q[1 * k0Tile] = make_float2(c[u].z, m[u].x);
             q[2 * k0Tile] = make_float2(m[u].y, m[u].z);
             q[3 * k0Tile] = make_float2(on ? n[u].x * kn : 0.0f, on ? n[u].y * kn : 0.0f);
-            q[4 * k0Tile] = make_float2(on ? n[u].z * kn : 0.0f, ox ? fmaf(x[u].x, kx, ax) : 0.0f);
-            q[5 * k0Tile] = make_float2(ox ? fmaf(x[u].y, kx, ay) : 0.0f, ox ? fmaf(x[u].z, kx, az) : 0.0f);
+            q[4 * k0Tile] = make_float2(on ? n[u].z * kn : 0.0f, ox ? fmaf(x[u].x, kx, an.x) : 0.0f);
+            q[5 * k0Tile] = make_float2(ox ? fmaf(x[u].y, kx, an.y) : 0.0f, ox ? fmaf(x[u].z, kx, an.z) : 0.0f);
         }
         __syncthreads();
         if (spatial) {
@@ -135,20 +132,12 @@ __global__ __launch_bounds__(k0W* k0H) void svgf_stage0_kernel(SvgfArgs a) {
     a.vout[ip] = make_float4(v.x / (D.x * D.x), v.y / (D.y * D.y), v.z / (D.z * D.z), 0.0f);
 }
 
-// ---- a pass: the tiled lattice form of denoise_kernel (lrt_denoise.hip, which explains the
-// tile, the branch-free taps and the anchor-relative world_pos). A workgroup filters kTileW columns
-// x kTileRows rows that lie s apart, so that every 5x5 tap falls on its own lattice; the LDS tile
-// holds 12 floats per pixel as six float2 planes: colour, normal / sigma, world_pos / sigma
-// relative to the anchor, and -- where the denoiser has albedo -- the variance. 48 KiB at s = 16.
+// ---- a pass: the lattice tile of lrt_atrous.h (which explains the tile, the branch-free taps and
+// the anchor-relative world_pos), as denoise_kernel; where the denoiser stages albedo, the variance.
 // The 3x3 variance pre-filter is undilated, off the lattice for s > 1: its nine taps are loaded
 // for the centre alone straight from global memory, issued ahead of the staging so that their
 // latency passes behind it (rows one apart: a wave's nine loads cover three 1 KiB runs, which its
 // neighbours in x and the next pass's phases share in L2).
-constexpr int kTileW = 64, kTileRows = 4, kTileLds = kTileRows + 4;
-constexpr int kPlanes = 6;
-inline int tile_width(int s) { return kTileW + 4 * s; }
-inline size_t tile_bytes(int s) { return sizeof(float2) * kPlanes * kTileLds * (size_t)tile_width(s); }
-
 // The last pass (a.last, a launch argument as denoise_kernel's rgb_only is) multiplies the albedo
 // back in from the centre's raw normal and albedo and stores 12 B. As a template parameter it
 // made the compiler issue all 150 LDS reads ahead of the first tap (256 VGPRs, one wave per SIMD,
@@ -158,13 +147,10 @@ __global__ __launch_bounds__(kTileW* kTileRows) void svgf_pass_kernel(SvgfArgs a
     const int s = a.s, tw = kTileW + 4 * s;
     const int plane = kTileLds * tw;   // float2s per plane
     const int tx = threadIdx.x, ty = threadIdx.y;
-    // blockIdx.y = group * s + phase: the rows y0 + r s, r = 0 .. kTileRows - 1
-    const int x0 = blockIdx.x * kTileW;
-    const int y0 = (blockIdx.y / s) * (kTileRows * s) + blockIdx.y % s;
+    const int x0 = blockIdx.x * kTileW, y0 = tile_y0(s);
     if (y0 >= a.h) return;   // the whole workgroup: the last group's unused phases
     const float kn = a.kn, kx = a.kx;
-    const float4 an = a.pos[(size_t)y0 * a.w + x0];   // uniform over the workgroup, inside the image
-    const float ax = finite_or_0(-an.x * kx), ay = finite_or_0(-an.y * kx), az = finite_or_0(-an.z * kx);   // -(anchor k)
+    const float3 an = tile_anchor(a.pos, a.w, x0, y0, kx);   // uniform over the workgroup
     const int px = x0 + tx, py = y0 + ty * s;
     const bool live = px < a.w && py < a.h;
     const int cpx = min(px, a.w - 1), cpy = min(py, a.h - 1);
@@ -180,16 +166,14 @@ __global__ __launch_bounds__(kTileW* kTileRows) void svgf_pass_kernel(SvgfArgs a
             pb[j * 3 + i] = gx >= 0 && gx < a.w && gy >= 0 && gy < a.h ? b3[i] * b3[j] : 0.0f;
             pv[j * 3 + i] = a.vin[(size_t)min(max(gy, 0), a.h - 1) * a.w + min(max(gx, 0), a.w - 1)];
         }
-    // stage: a thread takes up to kStage tile pixels (lattice rows ty and ty + kTileRows, columns
-    // tx and tx + kTileW), every load issued from a clamped address before the first LDS store
-    constexpr int kStage = 4;
-    static_assert(kTileLds == 2 * kTileRows, "two lattice rows per thread row");
-    static_assert(4 * (1 << (LRT_SVGF_MAX_ITER - 1)) <= kTileW, "two columns per thread cover the tile");
-    float4 c[kStage], vr[kStage], n[kStage], x[kStage];
-    bool ok[kStage];
+    // stage, straight-line: all of a thread's loads, then its LDS stores (tile_slot's arithmetic,
+    // written out: lrt_atrous.h says why)
+    static_assert(tile_covers(LRT_SVGF_MAX_ITER), "two columns per thread cover the tile");
+    float4 c[kTileStage], vr[kTileStage], n[kTileStage], x[kTileStage];
+    bool ok[kTileStage];
 #pragma unroll
-    for (int u = 0; u < kStage; ++u) {
-        const int lr = ty + (u >> 1) * kTileRows, cx = min(tx + (u & 1) * kTileW, tw - 1);
+    for (int u = 0; u < kTileStage; ++u) {
+        const int lr = tile_slot_row(u, ty), cx = min(tile_slot_col(u, tx), tw - 1);
         const int gy = y0 + (lr - 2) * s, gx = x0 - 2 * s + cx;
         ok[u] = gy >= 0 && gy < a.h && gx >= 0 && gx < a.w;
         const size_t ig = (size_t)min(max(gy, 0), a.h - 1) * a.w + min(max(gx, 0), a.w - 1);
@@ -199,18 +183,11 @@ __global__ __launch_bounds__(kTileW* kTileRows) void svgf_pass_kernel(SvgfArgs a
         x[u] = a.pos[ig];
     }
 #pragma unroll
-    for (int u = 0; u < kStage; ++u) {
-        const int lr = ty + (u >> 1) * kTileRows, cx = tx + (u & 1) * kTileW;
+    for (int u = 0; u < kTileStage; ++u) {
+        const int lr = tile_slot_row(u, ty), cx = tile_slot_col(u, tx);
         if (cx >= tw) continue;
         const bool on = ok[u] && a.has_n, ox = ok[u] && a.has_x;
-        const float4 cc = c[u], vv = vr[u], nn = n[u], xx = x[u];
-        float2* t = tile + lr * tw + cx;
-        t[0 * plane] = make_float2(ok[u] ? cc.x : 0.0f, ok[u] ? cc.y : 0.0f);
-        t[1 * plane] = make_float2(ok[u] ? cc.z : 0.0f, on ? nn.x * kn : 0.0f);
-        t[2 * plane] = make_float2(on ? nn.y * kn : 0.0f, on ? nn.z * kn : 0.0f);
-        t[3 * plane] = make_float2(ox ? fmaf(xx.x, kx, ax) : 0.0f, ox ? fmaf(xx.y, kx, ay) : 0.0f);
-        t[4 * plane] = make_float2(ox ? fmaf(xx.z, kx, az) : 0.0f, ok[u] ? vv.x : 0.0f);
-        t[5 * plane] = make_float2(ok[u] ? vv.y : 0.0f, ok[u] ? vv.z : 0.0f);
+        tile_store(tile + lr * tw + cx, plane, ok[u], on, ox, ok[u], c[u], n[u], x[u], vr[u], kn, kx, an, 1.0f);
     }
     float vt = 0.0f, bs = 0.0f;
 #pragma unroll
@@ -221,13 +198,12 @@ __global__ __launch_bounds__(kTileW* kTileRows) void svgf_pass_kernel(SvgfArgs a
     const float inv_c = 1.44269504f / (a.sc2 * (vt / bs) + 1e-6f);   // the centre is inside: bs >= 1/4
     __syncthreads();
     if (!live) return;
-    const float hw[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     float hx[5], hy[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
         const int gx = px + (i - 2) * s, gy = py + (i - 2) * s;
-        hx[i] = gx >= 0 && gx < a.w ? hw[i] : 0.0f;
-        hy[i] = gy >= 0 && gy < a.h ? hw[i] : 0.0f;
+        hx[i] = tile_spline(i, gx, a.w);
+        hy[i] = tile_spline(i, gy, a.h);
     }
     const float2* ctr = tile + (ty + 2) * tw + tx + 2 * s;
     const float2 p0 = ctr[0 * plane], p1 = ctr[1 * plane], p2 = ctr[2 * plane];
@@ -243,14 +219,7 @@ __global__ __launch_bounds__(kTileW* kTileRows) void svgf_pass_kernel(SvgfArgs a
             const float2 q0 = q[0 * plane], q1 = q[1 * plane], q2 = q[2 * plane];
             const float2 q3 = q[3 * plane], q4 = q[4 * plane], q5 = q[5 * plane];
             const float dx = p0.x - q0.x, dy = p0.y - q0.y, dz = p1.x - q1.x;
-            float e = (dx * dx + dy * dy + dz * dz) * inv_c;
-            float d;
-            d = p1.y - q1.y, e += d * d;
-            d = p2.x - q2.x, e += d * d;
-            d = p2.y - q2.y, e += d * d;
-            d = p3.x - q3.x, e += d * d;
-            d = p3.y - q3.y, e += d * d;
-            d = p4.x - q4.x, e += d * d;
+            const float e = tile_guide_dist((dx * dx + dy * dy + dz * dz) * inv_c, p1, p2, p3, p4, q1, q2, q3, q4);
             const float wq = hx[i] * __builtin_amdgcn_exp2f(-e);
             const float w2 = wq * wq;
             rr += wq * q0.x;
@@ -297,10 +266,7 @@ static hipError_t launch_stage0(const SvgfArgs& a, hipStream_t s) {
 }
 
 static hipError_t launch_pass(const SvgfArgs& a, hipStream_t s) {
-    const int groups = (a.h + kTileRows * a.s - 1) / (kTileRows * a.s);
-    const dim3 grid((unsigned)((a.w + kTileW - 1) / kTileW), (unsigned)(groups * a.s));
-    const dim3 block(kTileW, kTileRows);
-    svgf_pass_kernel<<<grid, block, tile_bytes(a.s), s>>>(a);
+    svgf_pass_kernel<<<tile_grid(a.w, a.h, a.s), dim3(kTileW, kTileRows), tile_bytes(a.s), s>>>(a);
     return hipGetLastError();
 }
 
@@ -308,8 +274,7 @@ static int validate_svgf(const lrt_svgf_desc* d, const float* color, const float
                          const float* out, const float* var) {
     if (!d) return fail(LRT_E_INVALID, "desc is NULL");
     if (!color || !moment2 || !out) return fail(LRT_E_INVALID, "color, moment2 or out is NULL");
-    if (d->width < 1 || d->height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    if ((long long)d->width * d->height > INT_MAX / 4) return fail(LRT_E_INVALID, "image too large");
+    if (int rc = validate_frame_size(d->width, d->height)) return rc;
     if (d->iterations < 1 || d->iterations > LRT_SVGF_MAX_ITER)
         return fail(LRT_E_INVALID, "iterations must be in 1..LRT_SVGF_MAX_ITER");
     if (d->flags != 0 || d->reserved != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
@@ -321,16 +286,13 @@ static int validate_svgf(const lrt_svgf_desc* d, const float* color, const float
     const size_t bytes = (size_t)d->width * d->height * 4 * sizeof(float);
     const float* const ins[5] = {color, moment2, g ? g->normal : nullptr, g ? g->world_pos : nullptr,
                                  g ? g->albedo : nullptr};
-    auto overlap = [bytes](const float* p, const float* q) {
-        const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-        return p && q && a < b + bytes && b < a + bytes;
-    };
     for (int j = 0; j < 5; ++j) {
-        if (overlap(out, ins[j]) && !(j == 0 && out == color))
+        if (ranges_overlap(out, bytes, ins[j], bytes) && !(j == 0 && out == color))
             return fail(LRT_E_INVALID, "aliasing: out overlaps an input (it may only be color itself)");
-        if (overlap(var, ins[j])) return fail(LRT_E_INVALID, "aliasing: variance_out overlaps an input");
+        if (ranges_overlap(var, bytes, ins[j], bytes))
+            return fail(LRT_E_INVALID, "aliasing: variance_out overlaps an input");
     }
-    if (overlap(out, var)) return fail(LRT_E_INVALID, "aliasing: out and variance_out overlap");
+    if (ranges_overlap(out, bytes, var, bytes)) return fail(LRT_E_INVALID, "aliasing: out and variance_out overlap");
     return LRT_OK;
 }
 
@@ -343,8 +305,7 @@ static int svgf_device(const lrt_svgf_desc* d, const float* color, const float* 
     const int K = d->iterations;
     const int ntmp = K == 1 ? 2 : 4;
     void* p = nullptr;
-    if (const hipError_t e = stream_scratch(s, ntmp * npix * sizeof(float4), &p))
-        return e == hipErrorOutOfMemory ? fail(LRT_E_NOMEM, "svgf scratch") : hip_fail(e, "svgf scratch");
+    if (int rc = scratch_or_fail(s, ntmp * npix * sizeof(float4), "svgf scratch", &p)) return rc;
     float4* const base = static_cast<float4*>(p);
     float4* const tc[2] = {base, ntmp == 4 ? base + 2 * npix : nullptr};
     float4* const tv[2] = {base + npix, ntmp == 4 ? base + 3 * npix : nullptr};
@@ -418,7 +379,7 @@ int lrt_svgf_filter_device(const lrt_svgf_desc* desc, const float* d_color, cons
     RoctxRange rr_("lrt_svgf_filter_device");
     if (int rc = validate_svgf(desc, d_color, d_moment2, d_guides, d_out, d_variance_out)) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_devs[0].ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);   // context 0's device (device 0 of lrt_initialize_devices)
     return svgf_device(desc, d_color, d_moment2, d_guides, d_out, d_variance_out, (hipStream_t)stream);
 }
@@ -428,7 +389,7 @@ int lrt_svgf_filter_host(const lrt_svgf_desc* desc, const float* color, const fl
     RoctxRange rr_("lrt_svgf_filter_host");
     if (int rc = validate_svgf(desc, color, moment2, guides, out, variance_out)) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_devs[0].ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     const size_t bytes = (size_t)desc->width * desc->height * 4 * sizeof(float);
     hipStream_t s = ctx().stream;
@@ -437,10 +398,7 @@ int lrt_svgf_filter_host(const lrt_svgf_desc* desc, const float* color, const fl
     // is color's.
     const float* const hin[5] = {color, moment2, guides ? guides->normal : nullptr,
                                  guides ? guides->world_pos : nullptr, guides ? guides->albedo : nullptr};
-    struct Mirror {
-        float* p = nullptr;
-        ~Mirror() { if (p) (void)hipFree(p); }
-    } m;
+    DeviceStaging<float> m;
     if (hipMalloc(&m.p, 7 * bytes) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(svgf staging)");
     const size_t quad = bytes / sizeof(float);
     float* din[5];

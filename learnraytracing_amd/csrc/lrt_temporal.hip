@@ -175,8 +175,7 @@ static int validate_temporal(const lrt_temporal_desc* d, const float* color, con
         return fail(LRT_E_INVALID, "next needs color, moment2, normal and world_pos");
     if (prev && (!prev->color || !prev->moment2 || !prev->normal || !prev->world_pos))
         return fail(LRT_E_INVALID, "prev needs color, moment2, normal and world_pos");
-    if (d->width < 1 || d->height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    if ((long long)d->width * d->height > INT_MAX / 4) return fail(LRT_E_INVALID, "image too large");
+    if (int rc = validate_frame_size(d->width, d->height)) return rc;
     if (d->flags != 0 || d->reserved != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
     if (d->min_history < 1) return fail(LRT_E_INVALID, "min_history must be >= 1");
     for (float v : {d->cur_scale, d->alpha_min, d->normal_min, d->pos_tol, d->short_std})
@@ -197,16 +196,13 @@ static int validate_temporal(const lrt_temporal_desc* d, const float* color, con
                                  prev ? prev->color : nullptr, prev ? prev->moment2 : nullptr,
                                  prev ? prev->normal : nullptr, prev ? prev->world_pos : nullptr,
                                  prev ? prev->albedo : nullptr};
-    auto overlap = [bytes](const float* p, const float* q) {
-        const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-        return p && q && a < b + bytes && b < a + bytes;
-    };
     for (int i = 0; i < 6; ++i) {
         for (int j = 0; j < 9; ++j)
-            if (overlap(outs[i], ins[j]))
+            if (ranges_overlap(outs[i], bytes, ins[j], bytes))
                 return fail(LRT_E_INVALID, "aliasing: an output buffer overlaps an input or a prev buffer");
         for (int j = i + 1; j < 6; ++j)
-            if (overlap(outs[i], outs[j])) return fail(LRT_E_INVALID, "aliasing: two output buffers overlap");
+            if (ranges_overlap(outs[i], bytes, outs[j], bytes))
+                return fail(LRT_E_INVALID, "aliasing: two output buffers overlap");
     }
     return LRT_OK;
 }
@@ -294,7 +290,7 @@ int lrt_temporal_accumulate_device(const lrt_temporal_desc* desc, const float* d
     RoctxRange rr_("lrt_temporal_accumulate_device");
     if (int rc = validate_temporal(desc, d_color, d_cur, d_prev, d_next, d_color_std)) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_devs[0].ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);   // context 0's device (device 0 of lrt_initialize_devices)
     return temporal_device(desc, d_color, d_cur, d_prev, d_next, d_color_std, (hipStream_t)stream);
 }
@@ -305,7 +301,7 @@ int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* col
     RoctxRange rr_("lrt_temporal_accumulate_host");
     if (int rc = validate_temporal(desc, color, cur, prev, next, color_std)) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_devs[0].ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     const size_t bytes = (size_t)desc->width * desc->height * 4 * sizeof(float);
     hipStream_t s = ctx().stream;
@@ -317,10 +313,7 @@ int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* col
                                  prev ? prev->normal : nullptr, prev ? prev->world_pos : nullptr};
     float* const hout[6] = {next->color, next->moment2, next->normal, next->world_pos,
                             cur->albedo ? next->albedo : nullptr, color_std};
-    struct Mirror {
-        float* p = nullptr;
-        ~Mirror() { if (p) (void)hipFree(p); }
-    } m;
+    DeviceStaging<float> m;
     if (hipMalloc(&m.p, 14 * bytes) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(temporal staging)");
     const size_t quad = bytes / sizeof(float);
     float* din[8];

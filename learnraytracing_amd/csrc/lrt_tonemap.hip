@@ -187,8 +187,7 @@ static int validate_tonemap(const lrt_tonemap_desc* d, const float* color, const
                             const uint32_t* hist, const float* out, const uint32_t* bgra) {
     if (!d) return fail(LRT_E_INVALID, "desc is NULL");
     if (!color) return fail(LRT_E_INVALID, "color is NULL");
-    if (d->width < 1 || d->height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    if ((long long)d->width * d->height > INT_MAX / 4) return fail(LRT_E_INVALID, "image too large");
+    if (int rc = validate_frame_size(d->width, d->height)) return rc;
     if (d->op != LRT_TM_LINEAR && d->op != LRT_TM_REINHARD && d->op != LRT_TM_ACES)
         return fail(LRT_E_INVALID, "op must be one of LRT_TM_*");
     if (d->auto_exposure != 0 && d->auto_exposure != 1) return fail(LRT_E_INVALID, "auto_exposure must be 0 or 1");
@@ -204,16 +203,15 @@ static int validate_tonemap(const lrt_tonemap_desc* d, const float* color, const
     if (!d->auto_exposure && !out && !bgra) return fail(LRT_E_INVALID, "nothing to do: no output and no metering");
     // bgra, histogram and state may overlap nothing; out may be color itself and otherwise not overlap it
     const size_t npix = (size_t)d->width * d->height;
-    struct Range { uintptr_t p; size_t n; };
-    const Range rc{(uintptr_t)color, npix * 16}, ro{(uintptr_t)out, npix * 16}, rb{(uintptr_t)bgra, npix * 4};
-    const Range rh{(uintptr_t)hist, kWords * sizeof(uint32_t)}, rs{(uintptr_t)state, sizeof(lrt_exposure_state)};
-    auto overlap = [](const Range& x, const Range& y) { return x.p && y.p && x.p < y.p + y.n && y.p < x.p + x.n; };
-    if (overlap(rb, rc) || overlap(rb, ro) || overlap(rb, rh) || overlap(rb, rs))
+    const size_t nc = npix * 16, nb = npix * 4, nh = kWords * sizeof(uint32_t), ns = sizeof(lrt_exposure_state);
+    if (ranges_overlap(bgra, nb, color, nc) || ranges_overlap(bgra, nb, out, nc) ||
+        ranges_overlap(bgra, nb, hist, nh) || ranges_overlap(bgra, nb, state, ns))
         return fail(LRT_E_INVALID, "aliasing: bgra overlaps another buffer");
-    if (overlap(rh, rc) || overlap(rh, ro) || overlap(rh, rs))
+    if (ranges_overlap(hist, nh, color, nc) || ranges_overlap(hist, nh, out, nc) || ranges_overlap(hist, nh, state, ns))
         return fail(LRT_E_INVALID, "aliasing: histogram overlaps another buffer");
-    if (overlap(rs, rc) || overlap(rs, ro)) return fail(LRT_E_INVALID, "aliasing: state overlaps another buffer");
-    if (overlap(ro, rc) && out != color)
+    if (ranges_overlap(state, ns, color, nc) || ranges_overlap(state, ns, out, nc))
+        return fail(LRT_E_INVALID, "aliasing: state overlaps another buffer");
+    if (ranges_overlap(out, nc, color, nc) && out != color)
         return fail(LRT_E_INVALID, "aliasing: out overlaps color (it may only be color itself)");
     return LRT_OK;
 }
@@ -228,8 +226,7 @@ static int tonemap_device(const lrt_tonemap_desc* d, const float* color, lrt_exp
         uint32_t* total = hist;
         if (!total) {
             void* p = nullptr;
-            if (const hipError_t e = stream_scratch(s, kWords * sizeof(uint32_t), &p))
-                return e == hipErrorOutOfMemory ? fail(LRT_E_NOMEM, "tonemap scratch") : hip_fail(e, "tonemap scratch");
+            if (int rc = scratch_or_fail(s, kWords * sizeof(uint32_t), "tonemap scratch", &p)) return rc;
             total = static_cast<uint32_t*>(p);
         }
         LRT_HIP(hipMemsetAsync(total, 0, kWords * sizeof(uint32_t), s));
@@ -298,7 +295,7 @@ int lrt_tonemap_device(const lrt_tonemap_desc* desc, const float* d_color, lrt_e
     RoctxRange rr_("lrt_tonemap_device");
     if (int rc = validate_tonemap(desc, d_color, d_state, d_histogram, d_out, d_bgra)) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_devs[0].ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);   // context 0's device (device 0 of lrt_initialize_devices)
     return tonemap_device(desc, d_color, d_state, d_histogram, d_out, d_bgra, (hipStream_t)stream);
 }
@@ -308,7 +305,7 @@ int lrt_tonemap_host(const lrt_tonemap_desc* desc, const float* color, lrt_expos
     RoctxRange rr_("lrt_tonemap_host");
     if (int rc = validate_tonemap(desc, color, state, histogram, out, bgra)) return rc;
     std::lock_guard<std::mutex> lk(g_mu);
-    if (!g_devs[0].ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     const size_t npix = (size_t)desc->width * desc->height;
     const size_t frame = npix * 4 * sizeof(float), words = kWords * sizeof(uint32_t);
@@ -317,10 +314,7 @@ int lrt_tonemap_host(const lrt_tonemap_desc* desc, const float* color, lrt_expos
     // Device mirrors in one allocation that lives for the call: color, out (copied in first: its
     // alpha stays; in place it is color's mirror), bgra, then the histogram and the state, which
     // are mirrored only when the call meters.
-    struct Mirror {
-        char* p = nullptr;
-        ~Mirror() { if (p) (void)hipFree(p); }
-    } m;
+    DeviceStaging<char> m;
     if (hipMalloc(&m.p, 2 * frame + npix * sizeof(uint32_t) + words + sizeof(lrt_exposure_state)) != hipSuccess)
         return fail(LRT_E_NOMEM, "hipMalloc(tonemap staging)");
     float* const d_color = reinterpret_cast<float*>(m.p);

@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HOLD_SECONDS = 0.025
-TILE_W, TILE_ROWS = 64, 4       # lrt_denoise.hip: kTileW, kTileRows
+TILE_W, TILE_ROWS = 64, 4       # lrt_atrous.h: kTileW, kTileRows
 MIN_BYTES_PER_PIXEL = 64        # colour + normal + world_pos + albedo, 16 B each, read once
 
 
