@@ -401,6 +401,11 @@ constexpr int kPoolPixOverlap = LRT_POOL_PIX_OVERLAP;
 #endif
 constexpr int kPoolSplit16Alone = LRT_POOL_SPLIT16_ALONE;
 constexpr int kPoolSplit16Overlap = LRT_POOL_SPLIT16_OVERLAP;
+// The least share a split tail gets in the five-wave slim instance (launch_pool)
+#ifndef LRT_POOL_SPLIT16_SLIM
+#define LRT_POOL_SPLIT16_SLIM 8
+#endif
+constexpr int kPoolSplit16Slim = LRT_POOL_SPLIT16_SLIM;
 // Is a pool launch of another stream than s still running (its scratch slot's last-use event)?
 hipError_t other_stream_busy(hipStream_t s, bool* busy);
 // sample mode's merge (merge_samples_kernel) on stream s

@@ -81,24 +81,68 @@ constexpr int kPoolGridWaves = 16;
 // material ids, 14 B a level instead of a float4's 16 -- so that 16 stacks of 8 levels take the
 // 112 KB that 7 float4 levels took and still fit beside the grid in the CU's 160 KB. (Round 4
 // had 7 float4 levels there and the eighth in the global overflow stack, whose per-lane
-// pointers also held registers.) Bytes per wave:
-template <int kW>
-constexpr int pool_stack_bytes() { return 64 * kTraceLdsLevels * (kW > 1 ? 14 : 16); }
+// pointers also held registers.)
+//
+// The trimmed fixed-scene depth-8 instance (kNL > 0, unchecked roots) is SLIM: the three float
+// planes alone (its material ids, 0..8, ride as eight 4-bit fields in one VGPR) and no copy of
+// the powf tables (powf5's slow path, 0.57 % of its domain, reads the __constant__ originals).
+// That is 6,144 + 528 + 608 = 7,280 B a block against 9,840 B, so that twenty one-wave blocks
+// fit in a CU's LDS and the instance runs at five waves per SIMD (pool_waves_per_eu).
+template <int MAXD, int kW, int kNL, bool kChk>
+constexpr bool pool_slim() { return MAXD <= kTraceLdsLevels && kW == 1 && kNL > 0 && !kChk; }
+// The kernel's __launch_bounds__: the slim instance's loop fits 96 VGPRs with its spills
+// outside the bounce loop (profiles/r8_occ); every other instance would carry up to 216 B of
+// scratch at five waves and keeps kWavesPerEU.
+#ifndef LRT_POOL_SLIM_WAVES
+#define LRT_POOL_SLIM_WAVES 5   // (A/B builds: the slim layout at four waves)
+#endif
+template <int MAXD, int kW, int kNL, bool kChk>
+constexpr int pool_waves_per_eu() { return pool_slim<MAXD, kW, kNL, kChk>() ? LRT_POOL_SLIM_WAVES : kWavesPerEU; }
+#ifndef LRT_POOL_SLIM_POW
+#define LRT_POOL_SLIM_POW 0   // (A/B builds: 1 keeps the slim instance's LDS copy of the powf tables, 7,792 B)
+#endif
+// A wave tracing fewer paths than this yields its SIMD's issue slots (pool_kernel, kLate)
+#ifndef LRT_POOL_PRIO_LANES
+#define LRT_POOL_PRIO_LANES 24
+#endif
+
+// The head of a block's dynamic LDS, for pool_kernel's carve-up and launch_pool's sizes alike:
+// [recursion stacks, one per wave][powf tables][renormalize table][scene ...]. Byte offsets.
+struct PoolLds {
+    int stack_w;   // one wave's recursion stack
+    int pow;       // the powf tables' copy (pow_b bytes; none: pow_b == 0)
+    int pow_b;
+    int lut;       // the renormalize table (lut_b bytes; none with an acceleration structure)
+    int lut_b;
+    int scene;     // spheres, materials, lights (kLds), then whatever a.bvh_stack_offset names
+};
+constexpr PoolLds pool_lds(int waves, bool slim, int acc) {
+    PoolLds l{};
+    l.stack_w = 64 * kTraceLdsLevels * (slim ? 12 : waves > 1 ? 14 : 16);
+    l.pow = l.stack_w * waves;
+    l.pow_b = slim && !LRT_POOL_SLIM_POW ? 0 : kPowTableBytes;
+    l.lut = l.pow + l.pow_b;
+    l.lut_b = acc ? 0 : kRenormBytes;
+    l.scene = l.lut + l.lut_b;
+    return l;
+}
 
 // kNL > 0: the scene has exactly kNL lights (ScatterDir); kChk = false: the closest-hit scan's
 // roots skip their range check (SphereRoots; the host proves the scene's radii allow it). Both are
 // taken together, by the depth-8 fixed-scene instance of the reference's own scene shape (9
 // spheres, one light), when launch_pool finds them to hold.
 template <int MAXD, bool kLds, int kAcc, int kPix, int kNS = 0, int kW = 1, int kNL = 0, bool kChk = true>
-__global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
+__global__ __launch_bounds__(64 * kW, (pool_waves_per_eu<MAXD, kW, kNL, kChk>())) void pool_kernel(
     const KernelArgs a) {
     static_assert(kNS == 0 || (kLds && !kAcc), "a fixed sphere count is for the LDS linear scan");
     static_assert((kNL == 0 && kChk) || kNS > 0, "a fixed light count and unchecked roots: fixed-scene instances");
     static_assert(kW == 1 || (kAcc == kAccGrid && !kLds), "multi-wave blocks: the grid instance");
     constexpr int kLv = kTraceLdsLevels;   // recursion stack levels in LDS
-    constexpr bool kPacked = kW > 1;        // (pool_stack_bytes)
+    constexpr bool kSlim = pool_slim<MAXD, kW, kNL, kChk>();
+    constexpr bool kPacked = kW > 1 || kSlim;   // float planes (pool_lds)
     // LDS as trace_kernel: [recursion stack kTraceLdsLevels x 64][powf tables][renormalize
     // table unless kAcc][spheres][materials][lights][bvh stack at a.bvh_stack_offset]
+    constexpr PoolLds kL = pool_lds(kW, kSlim, kAcc);
     extern __shared__ float4 smem[];
     const int lane = kW > 1 ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
     const int tid = threadIdx.x;   // fills of the block-shared LDS
@@ -107,8 +151,8 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
     const int wid = (int)blockIdx.x * kW + wave;
     const int nwaves = (int)gridDim.x * kW;
     (void)nwaves;
-    double* s_pow = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + kW * pool_stack_bytes<kW>());
-    {
+    double* s_pow = reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + kL.pow);
+    if constexpr (kL.pow_b > 0) {
         const libm::PowTables g = libm::pow_tables();
         for (int i = tid; i < 16; i += 64 * kW) {
             s_pow[i] = g.invc[i];
@@ -116,11 +160,9 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
         }
         for (int i = tid; i < 32; i += 64 * kW) reinterpret_cast<uint64_t*>(s_pow + 32)[i] = g.exp2[i];
     }
-    constexpr int kLutBytes = kAcc ? 0 : kRenormBytes;
-    float* s_lut = kAcc ? nullptr : reinterpret_cast<float*>(s_pow + 64);
+    float* s_lut = kAcc ? nullptr : reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + kL.lut);
     if (!kAcc) renorm_lut_fill(s_lut, lane, 64);
-    float4* s_sph = reinterpret_cast<float4*>(reinterpret_cast<char*>(smem) + kW * pool_stack_bytes<kW>() +
-                                              kPowTableBytes + kLutBytes);
+    float4* s_sph = reinterpret_cast<float4*>(reinterpret_cast<char*>(smem) + kL.scene);
     float4* s_mat = s_sph + a.count;
     int* s_lights = reinterpret_cast<int*>(s_mat + 3 * a.count);
     if (kLds) {
@@ -146,9 +188,13 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
     }
     __syncthreads();
     SceneView sc;
-    sc.pow.invc = s_pow;
-    sc.pow.logc = s_pow + 16;
-    sc.pow.exp2 = reinterpret_cast<const uint64_t*>(s_pow + 32);
+    if constexpr (kL.pow_b > 0) {
+        sc.pow.invc = s_pow;
+        sc.pow.logc = s_pow + 16;
+        sc.pow.exp2 = reinterpret_cast<const uint64_t*>(s_pow + 32);
+    } else {
+        sc.pow = libm::pow_tables();   // the __constant__ originals (powf5's slow path only)
+    }
     sc.rnlut = s_lut;
     sc.sph = kLds ? s_sph : a.sph;
     sc.mats = kLds ? s_mat : a.mats;
@@ -176,9 +222,12 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
     unsigned long long wlast = 0, wtiles = 0;   // the last task's start, the task count
 #endif
     float4* const lstk = smem + wave * kLv * 64 + lane;   // this lane's recursion stack (LDS)
-    // (packed: the x plane at lane, then y, z, and the u16 ids after the three float planes)
-    float* const pstk = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + wave * pool_stack_bytes<kW>()) + lane;
+    // (packed: the x plane at lane, then y, z, and the u16 ids after the three float planes;
+    // slim: no id plane, the lane's ids are the 4-bit fields of idw, level 0 lowest)
+    float* const pstk = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + wave * kL.stack_w) + lane;
     unsigned short* const pids = reinterpret_cast<unsigned short*>(pstk - lane + 3 * kLv * 64) + lane;
+    unsigned idw = 0;
+    static_assert(!kSlim || (kLv <= 8 && kNS <= 16), "slim: eight 4-bit ids in one register");
     const size_t gtid = (size_t)wid * 64 + lane;
     const size_t gthreads = (size_t)nwaves * 64;
     // Levels >= kLv (MAXD > 8) in the global overflow stack: a u16 per level (the
@@ -195,7 +244,10 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
                 pstk[lvl * 64] = v.x;
                 pstk[(kLv + lvl) * 64] = v.y;
                 pstk[(2 * kLv + lvl) * 64] = v.z;
-                pids[lvl * 64] = (unsigned short)__float_as_int(v.w);
+                if constexpr (kSlim)
+                    idw = (idw & ~(15u << (4 * lvl))) | ((unsigned)__float_as_int(v.w) << (4 * lvl));
+                else
+                    pids[lvl * 64] = (unsigned short)__float_as_int(v.w);
             } else {
                 lstk[lvl * 64] = v;
             }
@@ -210,7 +262,7 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
         if (MAXD <= kLv || lvl < kLv) {
             if constexpr (kPacked)
                 return make_float4(pstk[lvl * 64], pstk[(kLv + lvl) * 64], pstk[(2 * kLv + lvl) * 64],
-                                   __int_as_float((int)pids[lvl * 64]));
+                                   __int_as_float(kSlim ? (int)((idw >> (4 * lvl)) & 15u) : (int)pids[lvl * 64]));
             return lstk[lvl * 64];
         }
         const size_t o = (size_t)(lvl - kLv) * gthreads;
@@ -317,7 +369,12 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
                     }
                     const unsigned long long needM = waitM;
                     if (state == kPoolIdle) {
-                        k = next + __popcll(needM & below);
+                        // (slim: mbcnt counts the lanes below without the two registers of `below`)
+                        if constexpr (kSlim)
+                            k = next + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(needM >> 32),
+                                                                      __builtin_amdgcn_mbcnt_lo((unsigned)needM, 0u));
+                        else
+                            k = next + __popcll(needM & below);
                         state = kPoolDone;
                         if (k < N) {
                             const int j = k & ((1 << lgP) - 1), f = fr0 + (k >> lgP);
@@ -369,7 +426,7 @@ __global__ __launch_bounds__(64 * kW, kWavesPerEU) void pool_kernel(
                 // fuller waves beside it: config 2 alone 0.2598 -> 0.2527 ms, two streams and
                 // configs 3-4 within noise (profiles/r5_al); the depth-8 one-wave instances only
                 if constexpr (kLate) {
-                    if (__popcll(traceM) < 24) __builtin_amdgcn_s_setprio(0);
+                    if (__popcll(traceM) < LRT_POOL_PRIO_LANES) __builtin_amdgcn_s_setprio(0);
                     else __builtin_amdgcn_s_setprio(1);
                 }
                 // (no packet traversal here: without its code the instance keeps its traversal

@@ -36,8 +36,9 @@ int launch_pool(KernelArgs a, bool lds, int xc, int rows, hipStream_t s) {
                    ? fa.sharedSizeBytes
                    : (size_t)0;
     }();
+    constexpr PoolLds lw = pool_lds(kW, false, kAccGrid);   // the multi-wave grid block's head
     int wpb = acc == kAccGrid && !lds
-                  ? pool_grid_wpb(a, pool_stack_bytes<kW>(), kPowTableBytes + (bstk + 15) / 16 * 16, static_b, &grid_b)
+                  ? pool_grid_wpb(a, lw.stack_w, lw.pow_b + lw.lut_b + (bstk + 15) / 16 * 16, static_b, &grid_b)
                   : 1;
     if (wpb > 1) {
         // dynamic LDS above the default limit: raised once per device for this instance
@@ -55,18 +56,20 @@ int launch_pool(KernelArgs a, bool lds, int xc, int rows, hipStream_t s) {
         if (!r || *r < 0) wpb = 1;
     }
     const int lv = kTraceLdsLevels;   // recursion stack levels in LDS (packed in multi-wave blocks)
-    const size_t stack = (wpb > 1 ? (size_t)pool_stack_bytes<kW>() * wpb : (size_t)pool_stack_bytes<1>()) +
-                         kPowTableBytes + (acc ? 0 : kRenormBytes);
-    const size_t scene = lds ? sizeof(float4) * (4 * (size_t)a.count + (size_t)(a.nlights + 3) / 4 + 1) : 0;
-    a.bvh_stack_offset = (int)(stack + scene);
-    a.grid_lds_offset = wpb > 1 ? (int)(stack + (bstk + 15) / 16 * 16) : 0;
-    const size_t ldsb = wpb > 1 ? stack + (bstk + 15) / 16 * 16 + grid_b : stack + scene + bstk;
     const bool fixed = lds && acc == kAccScan && a.count == kFixedSpheres;
     // the fixed-scene instance trimmed to one light and unchecked roots (pool_kernel's kNL, kChk):
     // depth <= 8 only, and only for a scene that has one light and radii in the proven range
     // (upload_scene); every other scene keeps the general instances
     constexpr bool kTrimmed = MAXD <= 8;
     const bool trim = kTrimmed && fixed && a.nlights == 1 && ctx().roots_in_range;
+    static_assert(!kTrimmed || pool_slim<MAXD, 1, 1, false>(), "the trimmed instance is the slim one (pool_lds)");
+    // the kernel's own carve-up (pool_lds): stacks, tables, then the scene
+    const PoolLds l = pool_lds(wpb, trim, acc);
+    const size_t stack = (size_t)l.scene;
+    const size_t scene = lds ? sizeof(float4) * (4 * (size_t)a.count + (size_t)(a.nlights + 3) / 4 + 1) : 0;
+    a.bvh_stack_offset = (int)(stack + scene);
+    a.grid_lds_offset = wpb > 1 ? (int)(stack + (bstk + 15) / 16 * 16) : 0;
+    const size_t ldsb = wpb > 1 ? stack + (bstk + 15) / 16 * 16 + grid_b : stack + scene + bstk;
     const void* kern_trim = nullptr;
     if constexpr (kTrimmed) kern_trim = (const void*)pool_kernel<MAXD, true, kAccScan, kPix, kFixedSpheres, 1, 1, false>;
     const void* kern = trim ? kern_trim : acc == kAccGrid ? (lds ? (const void*)pool_kernel<MAXD, true, kAccGrid, kPix>
@@ -128,7 +131,11 @@ int launch_pool(KernelArgs a, bool lds, int xc, int rows, hipStream_t s) {
     // extra queue items: a queue without a block would leave them undone); a recording launch
     // times whole tiles
     const bool split = !a.tcost && wpb == 1 && a.lateFetch && blocks >= kV0Queues;
-    a.splitFrom = split ? (int)(ntiles - ntiles * a.split16 / 16) : (int)ntiles;
+    // (the slim instance's 5,120 waves leave a launch alone 2.8 tiles per wave instead of 3.5: where
+    // a split tail is asked for it takes a larger share, one stream 0.2392 -> 0.2355 ms at 8/16
+    // against 5/16 (0.2349 at four waves), profiles/r8_occ)
+    const int split16 = trim && a.split16 > 0 ? std::max(a.split16, kPoolSplit16Slim) : a.split16;
+    a.splitFrom = split ? (int)(ntiles - ntiles * split16 / 16) : (int)ntiles;
     bool probed = false;
     if (record == 1 && pool_probe_mode() > 0 && (pool_probe_mode() == 2 || !users[1])) {
         // no measured order to go by: probe the tiles' costs, sort them, and let this
