@@ -392,7 +392,8 @@ int lrt_denoise_host(const lrt_denoise_desc* desc, const float* color, const lrt
  * fresh samples. That is how a caller gets new seeds every time step without touching the render
  * kernels (a static camera re-rendering frame0 = 0 would accumulate identical frames).
  *
- * Limits: whole frames only. Static scene: the camera moves, the spheres do not. First-hit
+ * Limits: whole frames only. Static scene: the camera moves, the spheres do not (for spheres that
+ * move between two frames there is lrt_temporal_accumulate_moving_* below). First-hit
  * reprojection only: reflections and refractions lag. Like the denoiser it is not bit-pinned (the
  * reference has no such stage) but tolerance-checked against its NumPy restatement
  * (tests/temporal_ref.py); it is deterministic run to run. */
@@ -447,6 +448,70 @@ int lrt_temporal_accumulate_device(const lrt_temporal_desc* desc, const float* d
 int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* color, const lrt_features* cur,
                                  const lrt_temporal_state* prev, const lrt_temporal_state* next,
                                  float* color_std);
+
+/* The step under moving spheres. lrt_set_scene lets a caller move a sphere between two frames; the
+ * step above then reprojects every pixel as if its surface point had stood still, and either
+ * rejects the history of the moved sphere (a move of more than pos_tol x its distance: n stays 1
+ * for as long as it moves) or blends in another point of it. This form is given the two scenes.
+ * The scene is spheres only and a sphere moves rigidly (a translation and a uniform scale), so a
+ * pixel's own guides identify its sphere; the render kernels are not involved.
+ *
+ * With the spheres (c_i, r_i) of the scene the current frame was rendered with and (c'_i, r'_i)
+ * of the scene of the frame behind the previous state, steps 1-7 are those above, except:
+ *  2a. Match (hit pixels only). n^ = N / |N|; for each sphere i,
+ *      s_i = |X - (c_i + r_i n^)|^2: the squared distance from the pixel's mean hit point to the
+ *      point of sphere i whose outward normal is n^ (two spheres in contact have opposite normals
+ *      there, so the score separates them). Sphere i is a candidate iff r_i > 0 and r'_i > 0.
+ *      i* is the candidate of the smallest s_i, the lowest index on a tie. The pixel is matched iff
+ *      s_i* <= pos_tol^2 |X - O|^2 (the scale of the position test). A miss pixel is never matched;
+ *      a hit pixel without a match (its samples straddle two spheres, or its guides are not of
+ *      this scene) behaves exactly as in the static step.
+ *  3a. Carry back. If the pixel is matched and sphere i*'s eight floats differ in any bit between
+ *      the two arrays: Xc' = c'_i* + (r'_i* / r_i*) (Xc - c_i*). Otherwise Xc' = Xc, with no
+ *      arithmetic applied. The target of step 4 is d = Xc' - O' for a hit.
+ *  5a. The position test is |X'(Q) - Xc'|^2 <= pos_tol^2 |Xc - O|^2. The normal test is unchanged:
+ *      a translation with a uniform scale keeps normals.
+ * Under bit-identical cameras a pixel takes its own centre (as above) only if its Xc' = Xc; a
+ * moved sphere always goes through the projection.
+ * motion (optional, a whole frame of RGBA float quads, all four channels written):
+ *      x = fx - x, y = fy - y   the previous position minus the current one, in pixels
+ *      z = i* as a float, or -1 for an unmatched or a miss pixel
+ *      w = 1 if step 4 found a projectable point, else 0 (then x = y = 0)
+ * It says nothing about whether the taps counted: n says that. Without a previous state there is
+ * nothing to reproject into: motion is (0, 0, -1, 0) everywhere.
+ *
+ * Limits: first-hit motion only. The shadow, the reflection and the refraction of a moving sphere
+ * lag, as reflections already do. A moving emissive sphere changes the lighting everywhere, and the
+ * history follows at alpha_min. Spheres do not rotate visibly (materials are uniform). Whole frames
+ * only. */
+typedef struct lrt_scene_motion {
+    const lrt_sphere* spheres;       /* HOST: the scene the current frame was rendered with   */
+    const lrt_sphere* prev_spheres;  /* HOST: the scene of the frame behind the previous state */
+    int32_t count;                   /* 1..LRT_MAX_SPHERES, the same spheres in the same order */
+    int32_t reserved;                /* 0 */
+} lrt_scene_motion;
+
+/* lrt_temporal_accumulate_device under moving spheres. Both sphere arrays are read from host
+ * memory before the call returns (as lrt_set_scene reads its arrays). Up to 64 spheres travel in
+ * the kernel's own arguments; more are uploaded on `stream` into that stream's scratch, with no
+ * host round trip and no synchronisation (with sixteen uploads all still in flight, the call waits
+ * for the oldest). Either way back-to-back calls with different scenes each use their own.
+ * d_motion may be NULL.
+ *
+ * LRT_E_INVALID, before any device use: everything lrt_temporal_accumulate_device rejects; a NULL
+ * `scene` or a NULL array in it; count outside 1..LRT_MAX_SPHERES; reserved != 0; a non-finite
+ * float in either array; d_motion overlapping any other buffer (by address range). A sphere of
+ * radius <= 0 in either array is no error: it is never matched. */
+int lrt_temporal_accumulate_moving_device(const lrt_temporal_desc* desc, const lrt_scene_motion* scene,
+                                          const float* d_color, const lrt_features* d_cur,
+                                          const lrt_temporal_state* d_prev, const lrt_temporal_state* d_next,
+                                          float* d_color_std, float* d_motion, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_temporal_accumulate_moving_device's bit for bit. */
+int lrt_temporal_accumulate_moving_host(const lrt_temporal_desc* desc, const lrt_scene_motion* scene,
+                                        const float* color, const lrt_features* cur, const lrt_temporal_state* prev,
+                                        const lrt_temporal_state* next, float* color_std, float* motion);
 
 /* ---- variance-guided filter over the temporal state ------------------------------ */
 

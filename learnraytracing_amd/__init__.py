@@ -12,7 +12,8 @@ from .renderer import (DrawTest, InitializeDevices, InitializeTest, Job, Shutdow
                        pinned_backbuffer, get_scene, render_device, render_host, render_host_features,
                        render_tensor, render_tensor_features, render_tensor_to_frame, set_scene, shard_rows,
                        svgf_desc, svgf_filter_host, svgf_filter_tensor,
-                       temporal_accumulate_host, temporal_accumulate_tensor, temporal_desc,
+                       temporal_accumulate_host, temporal_accumulate_moving_host, temporal_accumulate_moving_tensor,
+                       temporal_accumulate_tensor, temporal_desc,
                        tonemap_desc, tonemap_host, tonemap_tensor)
 from .scene import default_scene, random_scene  # noqa: F401
 

@@ -115,6 +115,11 @@ class TemporalState(ctypes.Structure):        # lrt_temporal_state
                 ("world_pos", ctypes.c_void_p), ("albedo", ctypes.c_void_p)]
 
 
+class SceneMotion(ctypes.Structure):          # lrt_scene_motion
+    _fields_ = [("spheres", ctypes.POINTER(Sphere)), ("prev_spheres", ctypes.POINTER(Sphere)),
+                ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 TEMPORAL_STATE_NAMES = ("color", "moment2", "normal", "world_pos", "albedo")
 TEMPORAL_CUR_NAMES = ("normal", "world_pos", "albedo")   # what lrt_temporal_* reads of lrt_features
 TEMPORAL_PARAMS = ("cur_scale", "alpha_min", "normal_min", "pos_tol", "short_std", "min_history")
@@ -200,6 +205,12 @@ SIGNATURES = {
                                             _c.POINTER(TemporalState), _c.POINTER(TemporalState), _vp, _vp]),
     "lrt_temporal_accumulate_host": (_i, [_c.POINTER(TemporalDesc), _vp, _c.POINTER(Features),
                                           _c.POINTER(TemporalState), _c.POINTER(TemporalState), _vp]),
+    "lrt_temporal_accumulate_moving_device": (_i, [_c.POINTER(TemporalDesc), _c.POINTER(SceneMotion), _vp,
+                                                   _c.POINTER(Features), _c.POINTER(TemporalState),
+                                                   _c.POINTER(TemporalState), _vp, _vp, _vp]),
+    "lrt_temporal_accumulate_moving_host": (_i, [_c.POINTER(TemporalDesc), _c.POINTER(SceneMotion), _vp,
+                                                 _c.POINTER(Features), _c.POINTER(TemporalState),
+                                                 _c.POINTER(TemporalState), _vp, _vp]),
     "lrt_svgf_default": (_i, [_i, _i, _c.POINTER(SvgfDesc)]),
     "lrt_svgf_filter_device": (_i, [_c.POINTER(SvgfDesc), _vp, _vp, _c.POINTER(Features), _vp, _vp, _vp]),
     "lrt_svgf_filter_host": (_i, [_c.POINTER(SvgfDesc), _vp, _vp, _c.POINTER(Features), _vp, _vp]),

@@ -88,6 +88,11 @@ void free_context(Context& c) {
         if (sc.p) (void)hipFree(sc.p);
         if (sc.ev) (void)hipEventDestroy(sc.ev);
     }
+    for (auto& m : c.motion_slots) {
+        if (m.h) (void)hipHostFree(m.h);
+        if (m.ev) (void)hipEventDestroy(m.ev);
+    }
+    c.motion_slots.clear();
     for (auto& o : c.order) {
         if (o.d_base) (void)hipFree(o.d_base);
         if (o.ev_rec) (void)hipEventDestroy(o.ev_rec);

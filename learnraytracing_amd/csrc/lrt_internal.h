@@ -208,6 +208,18 @@ struct Context {
     static constexpr unsigned long long kScratchIdle = 64;
     static constexpr int kScratchSlots = 8;
     Scratch scratch[kScratchSlots];
+    // Page-locked upload slots of lrt_temporal_accumulate_moving_* (lrt_temporal.hip): the call
+    // packs its two sphere arrays into one (that is when the caller's arrays are read) and copies
+    // it to the stream's scratch asynchronously; `ev` follows the copy, and a slot is taken again
+    // only once it has passed. Slots are added while all are in flight, up to kMotionSlots.
+    struct MotionSlot {
+        void* h = nullptr;
+        hipEvent_t ev = nullptr;
+    };
+    static constexpr int kMotionSlots = 16;
+    static constexpr size_t kMotionSlotBytes = 2 * (size_t)LRT_MAX_SPHERES * 16;
+    std::vector<MotionSlot> motion_slots;
+    unsigned motion_next = 0;
     static constexpr int kOrderSlots = 8;
     TileOrder order[kOrderSlots];
     unsigned long long order_tick = 0;

@@ -5,6 +5,12 @@
 // launch per step, no atomics, no LDS (the reprojection offset is arbitrary per pixel: a fixed
 // halo does not fit). Not bit-pinned (the reference has no such stage): contraction is allowed
 // here, unlike in the render units.
+//
+// The moving form (lrt_temporal_accumulate_moving_*) is the same pixel function with kMove set: a
+// hit pixel first finds its sphere among the scene's (a wave-uniform loop over the packed current
+// spheres, read through uniform loads: no LDS, no barrier), is carried back with it, and may write
+// a motion vector. The spheres come in the kernel's arguments (up to kInlineSpheres) or from the
+// stream's scratch. The static instances compile without any of it.
 #include "lrt_internal.h"
 
 #pragma clang fp contract(fast)
@@ -34,6 +40,24 @@ struct TemporalArgs {
     int same_cam;                  // the two cameras are the same bits
 };
 
+// What the moving form adds. The two arrays are packed by the host (pack_motion): sph[i] = (c_i,
+// r_i), or radius -1 where sphere i is no candidate (r_i <= 0 or r'_i <= 0); psph[i] = (c'_i,
+// r'_i / r_i), or ratio -1 where the sphere's eight floats are the same bits in both scenes.
+struct MotionArgs {
+    const float4* sph;
+    const float4* psph;
+    float4* motion;   // or null
+    int count;
+};
+// A scene of up to kInlineSpheres spheres travels in the kernel's arguments instead (the packed
+// arrays back to back, psph at v + count): no upload, hence no copy command between two steps'
+// kernels, which at 9 spheres cost more than the match itself.
+constexpr int kInlineSpheres = 64;
+struct InlineSpheres {
+    float4 v[2 * kInlineSpheres];
+};
+constexpr int kMoveOff = 0, kMoveScratch = 1, kMoveInline = 2;   // temporal_pixel's kMove
+
 LRT_DEV float3 rgb(const float4 v) { return make_float3(v.x, v.y, v.z); }
 LRT_DEV float dot3(const float3 a, const float3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 LRT_DEV float3 sub3(const float3 a, const float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -47,10 +71,16 @@ LRT_DEV float3 mad3(const float s, const float3 a, const float3 b) {   // s a + 
 // (the denoiser's shape), alternating in one process: 3 % faster on the orbit, 6 % under a static
 // camera.
 constexpr int kBlockW = 32, kBlockH = 8;
+constexpr int kMatchBatch = 4;   // spheres per trip of the moving form's match loop
 
-// kHist: there is a previous state (else every pixel is reset).
-template <bool kHist>
-__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_kernel(TemporalArgs a) {
+// One pixel of the step. kHist: there is a previous state (else every pixel is reset). kMove: the
+// moving form (m is read only then), its spheres at m.sph / m.psph (kMoveScratch) or in the
+// kernel's own arguments at isph (kMoveInline).
+template <bool kHist, int kMove>
+__device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const MotionArgs& m,
+                                               const float4* isph = nullptr) {
+    const float4* const sph = kMove == kMoveInline ? isph : m.sph;
+    const float4* const psph = kMove == kMoveInline ? isph + m.count : m.psph;
     const int t = threadIdx.x;   // wave t / 64, its lane's pixel (t % 8, t / 8 % 8)
     const int x = blockIdx.x * kBlockW + (t >> 6) * 8 + (t & 7), y = blockIdx.y * kBlockH + ((t >> 3) & 7);
     if (x >= a.w || y >= a.h) return;
@@ -64,8 +94,10 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_kernel(TemporalArgs
     const float3 X = make_float3(k * x4.x, k * x4.y, k * x4.z);
     float3 col = C, m2 = make_float3(C.x * C.x, C.y * C.y, C.z * C.z);
     float n = 1.0f;
+    float4 mv = make_float4(0.0f, 0.0f, -1.0f, 0.0f);   // kMove: the motion vector
     if (kHist) {
-        const bool hit = dot3(N, N) >= 0.25f;
+        const float nn = dot3(N, N);
+        const bool hit = nn >= 0.25f;
         const float u = ((float)x + 0.5f) / (float)a.w, v = ((float)y + 0.5f) / (float)a.h;
         const float3 D = mad3(v, a.V, mad3(u, a.H, a.LO));
         // the pixel centre's surface point
@@ -81,17 +113,51 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_kernel(TemporalArgs
                 }
             }
         }
+        // kMove: the sphere whose point of outward normal N / |N| lies nearest X (the index is
+        // wave-uniform: scalar loads; a wave of misses skips the loop), then the centre's point
+        // carried back with it, Xp. Xp = Xc bit for bit unless that sphere moved.
+        float3 Xp = Xc;
+        bool moved = false;
+        if (kMove && hit) {
+            const float rn = 1.0f / sqrtf(nn);
+            const float3 nh = make_float3(rn * N.x, rn * N.y, rn * N.z);
+            float best = INFINITY;
+            int id = -1;
+            for (int i0 = 0; i0 < m.count; i0 += kMatchBatch) {
+                float4 s[kMatchBatch];   // a batch of loads in flight per trip, the last one clamped
+#pragma unroll
+                for (int j = 0; j < kMatchBatch; ++j) s[j] = sph[min(i0 + j, m.count - 1)];
+#pragma unroll
+                for (int j = 0; j < kMatchBatch; ++j) {
+                    const float3 e = sub3(X, mad3(s[j].w, nh, rgb(s[j])));
+                    const float sc = dot3(e, e);
+                    if (i0 + j < m.count && s[j].w > 0.0f && sc < best) {
+                        best = sc;
+                        id = i0 + j;
+                    }
+                }
+            }
+            const float3 XO0 = sub3(X, a.O);
+            if (id >= 0 && best <= a.pos_tol2 * dot3(XO0, XO0)) {
+                mv.z = (float)id;
+                const float4 p = psph[id];
+                if (p.w >= 0.0f) {
+                    moved = true;
+                    Xp = mad3(p.w, sub3(Xc, rgb(sph[id])), rgb(p));
+                }
+            }
+        }
         // into the previous camera. Under the same camera a pixel-centre point (and a miss) lands
         // on its own pixel centre exactly: taken as such, because the ~1e-5 px that the f32
         // projection is off by would bleed the neighbours in at every step of a static accumulation.
         float fx, fy;
         bool ok;
-        if (a.same_cam && (centred || !hit)) {
+        if (a.same_cam && (centred || !hit) && !moved) {
             fx = (float)x;
             fy = (float)y;
             ok = true;
         } else {
-            const float3 d = hit ? sub3(Xc, a.pO) : D;
+            const float3 d = hit ? sub3(Xp, a.pO) : D;
             const float da = dot3(d, a.pa);
             const float3 q = sub3(mad3(-a.fd / da, d, make_float3(0.0f, 0.0f, 0.0f)), a.pLO);
             fx = dot3(q, a.pH) * a.rhh * (float)a.w - 0.5f;
@@ -99,6 +165,7 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_kernel(TemporalArgs
             ok = da < 0.0f && fabsf(fx) < 1e6f && fabsf(fy) < 1e6f;   // (a NaN fails both compares)
         }
         if (!ok) fx = fy = 0.0f;
+        if (kMove && ok) mv.x = fx - (float)x, mv.y = fy - (float)y, mv.w = 1.0f;
         const float flx = floorf(fx), fly = floorf(fy);
         const int x0 = (int)flx, y0 = (int)fly;
         const float tx = fx - flx, ty = fy - fly;
@@ -124,7 +191,7 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_kernel(TemporalArgs
             const float b = ((i & 1) ? tx : 1.0f - tx) * ((i >> 1) ? ty : 1.0f - ty);
             const float3 Np = rgb(qn[i]);
             const bool hitp = dot3(Np, Np) >= 0.25f;
-            const float3 dX = sub3(rgb(qx[i]), Xc);
+            const float3 dX = sub3(rgb(qx[i]), Xp);
             const bool same = hit ? hitp && dot3(Np, N) >= a.normal_min && dot3(dX, dX) <= lim : !hitp;
             const float bw = in[i] && same ? b : 0.0f;
             sw += bw;
@@ -158,6 +225,24 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_kernel(TemporalArgs
         os[1] = sd.y;
         os[2] = sd.z;
     }
+    if (kMove && m.motion) m.motion[ip] = mv;
+}
+
+template <bool kHist>
+__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_kernel(TemporalArgs a) {
+    temporal_pixel<kHist, kMoveOff>(a, MotionArgs{});
+}
+
+// The moving form: the same block of 8 x 8-pixel waves.
+template <bool kHist>
+__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_moving_kernel(TemporalArgs a, MotionArgs m) {
+    temporal_pixel<kHist, kMoveScratch>(a, m);
+}
+
+// ... with the spheres in the arguments (count <= kInlineSpheres).
+__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_moving_inline_kernel(TemporalArgs a, MotionArgs m,
+                                                                                  InlineSpheres sc) {
+    temporal_pixel<true, kMoveInline>(a, m, sc.v);
 }
 
 static float3 f3(const lrt_float3& v) { return make_float3(v.x, v.y, v.z); }
@@ -207,10 +292,101 @@ static int validate_temporal(const lrt_temporal_desc* d, const float* color, con
     return LRT_OK;
 }
 
-// The step on stream s (device pointers, validated).
+// What lrt_temporal_accumulate_moving_* checks on top of validate_temporal (which has passed).
+static int validate_motion(const lrt_temporal_desc* d, const lrt_scene_motion* sm, const float* color,
+                           const lrt_features* cur, const lrt_temporal_state* prev, const lrt_temporal_state* next,
+                           const float* std, const float* motion) {
+    if (!sm || !sm->spheres || !sm->prev_spheres)
+        return fail(LRT_E_INVALID, "scene motion needs spheres and prev_spheres");
+    if (sm->count < 1 || sm->count > LRT_MAX_SPHERES) return fail(LRT_E_INVALID, "sphere count out of range");
+    if (sm->reserved != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
+    for (const lrt_sphere* arr : {sm->spheres, sm->prev_spheres})
+        for (int i = 0; i < sm->count; ++i)
+            for (float v : {arr[i].center.x, arr[i].center.y, arr[i].center.z, arr[i].radius})
+                if (!std::isfinite(v)) return fail(LRT_E_INVALID, "spheres must be finite");
+    const size_t bytes = (size_t)d->width * d->height * 4 * sizeof(float);
+    const float* const others[15] = {color, cur->normal, cur->world_pos, cur->albedo,
+                                     prev ? prev->color : nullptr, prev ? prev->moment2 : nullptr,
+                                     prev ? prev->normal : nullptr, prev ? prev->world_pos : nullptr,
+                                     prev ? prev->albedo : nullptr,
+                                     next->color, next->moment2, next->normal, next->world_pos, next->albedo, std};
+    for (const float* o : others)
+        if (ranges_overlap(motion, bytes, o, bytes))
+            return fail(LRT_E_INVALID, "aliasing: motion overlaps another buffer");
+    return LRT_OK;
+}
+
+// The two sphere arrays as the kernel reads them (MotionArgs), 2 x count float4 into dst.
+static void pack_motion(const lrt_scene_motion* sm, float4* dst) {
+    const int n = sm->count;
+    for (int i = 0; i < n; ++i) {
+        const lrt_sphere &c = sm->spheres[i], &p = sm->prev_spheres[i];
+        const bool cand = c.radius > 0.0f && p.radius > 0.0f;
+        const bool differs = memcmp(&c, &p, sizeof(c)) != 0;
+        dst[i] = make_float4(c.center.x, c.center.y, c.center.z, cand ? c.radius : -1.0f);
+        dst[n + i] = make_float4(p.center.x, p.center.y, p.center.z, cand && differs ? p.radius / c.radius : -1.0f);
+    }
+}
+
+// A page-locked slot whose last upload has completed (Context::motion_slots): a free one, a new
+// one, or, with kMotionSlots uploads all still in flight, the oldest after waiting for it.
+static int motion_slot(Context& c, Context::MotionSlot** out) {
+    for (auto& m : c.motion_slots) {
+        bool done = false;
+        LRT_HIP(event_done(m.ev, &done));
+        if (done) {
+            *out = &m;
+            return LRT_OK;
+        }
+    }
+    if ((int)c.motion_slots.size() < Context::kMotionSlots) {
+        Context::MotionSlot m;
+        if (hipHostMalloc(&m.h, Context::kMotionSlotBytes, hipHostMallocDefault) != hipSuccess)
+            return fail(LRT_E_NOMEM, "hipHostMalloc(sphere upload)");
+        const hipError_t e = hipEventCreateWithFlags(&m.ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            (void)hipHostFree(m.h);
+            return hip_fail(e, "hipEventCreateWithFlags");
+        }
+        c.motion_slots.push_back(m);
+        *out = &c.motion_slots.back();
+        return LRT_OK;
+    }
+    Context::MotionSlot& m = c.motion_slots[c.motion_next++ % Context::kMotionSlots];
+    LRT_HIP(hipEventSynchronize(m.ev));
+    *out = &m;
+    return LRT_OK;
+}
+
+// The packed spheres into stream s's scratch, in stream order: the host arrays are read here, into
+// a page-locked slot, and the copy out of it is asynchronous. *ma gets the device pointers.
+static int upload_motion(const lrt_scene_motion* sm, hipStream_t s, MotionArgs* ma) {
+    Context::MotionSlot* slot = nullptr;
+    if (int rc = motion_slot(ctx(), &slot)) return rc;
+    const size_t bytes = 2 * (size_t)sm->count * sizeof(float4);
+    void* d = nullptr;
+    if (int rc = scratch_or_fail(s, bytes, "temporal scratch", &d)) return rc;
+    pack_motion(sm, static_cast<float4*>(slot->h));
+    LRT_HIP(hipMemcpyAsync(d, slot->h, bytes, hipMemcpyHostToDevice, s));
+    LRT_HIP(hipEventRecord(slot->ev, s));
+    ma->sph = static_cast<const float4*>(d);
+    ma->psph = ma->sph + sm->count;
+    ma->count = sm->count;
+    return LRT_OK;
+}
+
+// The step on stream s (device pointers, validated). sm: the moving form (its spheres are read
+// here: packed into the kernel's arguments, or uploaded), with motion or without.
 static int temporal_device(const lrt_temporal_desc* d, const float* color, const lrt_features* cur,
                            const lrt_temporal_state* prev, const lrt_temporal_state* next, float* std,
-                           hipStream_t s) {
+                           hipStream_t s, const lrt_scene_motion* sm = nullptr, float* motion = nullptr) {
+    MotionArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.motion = reinterpret_cast<float4*>(motion);
+    const bool inl = sm && prev && sm->count <= kInlineSpheres;   // the spheres in the kernel's arguments
+    const bool upl = sm && prev && !inl;                         // ... or uploaded to the stream's scratch
+    if (upl)
+        if (int rc = upload_motion(sm, s, &ma)) return rc;
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
     auto q = [](const float* p) { return reinterpret_cast<const float4*>(p); };
@@ -251,11 +427,22 @@ static int temporal_device(const lrt_temporal_desc* d, const float* color, const
     a.same_cam = same(c.origin, p.origin) && same(c.a, p.a) && same(c.lowerLeftCorner, p.lowerLeftCorner) &&
                  same(c.horizontalVec, p.horizontalVec) && same(c.verticalVec, p.verticalVec);
     const dim3 grid((unsigned)((a.w + kBlockW - 1) / kBlockW), (unsigned)((a.h + kBlockH - 1) / kBlockH));
-    if (prev)
+    if (inl) {
+        InlineSpheres sc;
+        memset(&sc, 0, sizeof(sc));
+        pack_motion(sm, sc.v);
+        ma.count = sm->count;
+        temporal_moving_inline_kernel<<<grid, kBlockW * kBlockH, 0, s>>>(a, ma, sc);
+    } else if (upl)
+        temporal_moving_kernel<true><<<grid, kBlockW * kBlockH, 0, s>>>(a, ma);
+    else if (sm)   // nothing to reproject into: motion is (0, 0, -1, 0)
+        temporal_moving_kernel<false><<<grid, kBlockW * kBlockH, 0, s>>>(a, ma);
+    else if (prev)
         temporal_kernel<true><<<grid, kBlockW * kBlockH, 0, s>>>(a);
     else
         temporal_kernel<false><<<grid, kBlockW * kBlockH, 0, s>>>(a);
     LRT_HIP(hipGetLastError());
+    if (upl) LRT_HIP(stream_scratch_used(s));
     return LRT_OK;
 }
 
@@ -295,26 +482,25 @@ int lrt_temporal_accumulate_device(const lrt_temporal_desc* desc, const float* d
     return temporal_device(desc, d_color, d_cur, d_prev, d_next, d_color_std, (hipStream_t)stream);
 }
 
-int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* color, const lrt_features* cur,
-                                 const lrt_temporal_state* prev, const lrt_temporal_state* next,
-                                 float* color_std) {
-    RoctxRange rr_("lrt_temporal_accumulate_host");
-    if (int rc = validate_temporal(desc, color, cur, prev, next, color_std)) return rc;
+// The host forms (validated): sm and motion as temporal_device takes them.
+static int temporal_host(const lrt_temporal_desc* desc, const float* color, const lrt_features* cur,
+                         const lrt_temporal_state* prev, const lrt_temporal_state* next, float* color_std,
+                         const lrt_scene_motion* sm, float* motion) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     const size_t bytes = (size_t)desc->width * desc->height * 4 * sizeof(float);
     hipStream_t s = ctx().stream;
     // Every buffer goes through a device mirror of its own, all in one allocation that lives for
-    // the call: 4 inputs, 4 of the previous state, 6 outputs. The two outputs whose alpha stays
-    // (next->color, color_std) are copied in first.
+    // the call: 4 inputs, 4 of the previous state, 6 outputs and the motion frame. The two outputs
+    // whose alpha stays (next->color, color_std) are copied in first.
     const float* const hin[8] = {color, cur->normal, cur->world_pos, cur->albedo,
                                  prev ? prev->color : nullptr, prev ? prev->moment2 : nullptr,
                                  prev ? prev->normal : nullptr, prev ? prev->world_pos : nullptr};
     float* const hout[6] = {next->color, next->moment2, next->normal, next->world_pos,
                             cur->albedo ? next->albedo : nullptr, color_std};
     DeviceStaging<float> m;
-    if (hipMalloc(&m.p, 14 * bytes) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(temporal staging)");
+    if (hipMalloc(&m.p, (motion ? 15 : 14) * bytes) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(temporal staging)");
     const size_t quad = bytes / sizeof(float);
     float* din[8];
     float* dout[6];
@@ -333,11 +519,44 @@ int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* col
     dcur.albedo = din[3];
     const lrt_temporal_state dprev = {din[4], din[5], din[6], din[7], nullptr};
     const lrt_temporal_state dnext = {dout[0], dout[1], dout[2], dout[3], dout[4]};
-    if (int rc = temporal_device(desc, din[0], &dcur, prev ? &dprev : nullptr, &dnext, dout[5], s)) return rc;
+    float* const dmotion = motion ? m.p + 14 * quad : nullptr;
+    if (int rc = temporal_device(desc, din[0], &dcur, prev ? &dprev : nullptr, &dnext, dout[5], s, sm, dmotion))
+        return rc;
     for (int i = 0; i < 6; ++i)
         if (hout[i]) LRT_HIP(hipMemcpyAsync(hout[i], dout[i], bytes, hipMemcpyDeviceToHost, s));
+    if (motion) LRT_HIP(hipMemcpyAsync(motion, dmotion, bytes, hipMemcpyDeviceToHost, s));
     LRT_HIP(hipStreamSynchronize(s));
     return LRT_OK;
+}
+
+int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* color, const lrt_features* cur,
+                                 const lrt_temporal_state* prev, const lrt_temporal_state* next,
+                                 float* color_std) {
+    RoctxRange rr_("lrt_temporal_accumulate_host");
+    if (int rc = validate_temporal(desc, color, cur, prev, next, color_std)) return rc;
+    return temporal_host(desc, color, cur, prev, next, color_std, nullptr, nullptr);
+}
+
+int lrt_temporal_accumulate_moving_device(const lrt_temporal_desc* desc, const lrt_scene_motion* scene,
+                                          const float* d_color, const lrt_features* d_cur,
+                                          const lrt_temporal_state* d_prev, const lrt_temporal_state* d_next,
+                                          float* d_color_std, float* d_motion, void* stream) {
+    RoctxRange rr_("lrt_temporal_accumulate_moving_device");
+    if (int rc = validate_temporal(desc, d_color, d_cur, d_prev, d_next, d_color_std)) return rc;
+    if (int rc = validate_motion(desc, scene, d_color, d_cur, d_prev, d_next, d_color_std, d_motion)) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (int rc = require_initialized()) return rc;
+    DeviceScope ds_(0);
+    return temporal_device(desc, d_color, d_cur, d_prev, d_next, d_color_std, (hipStream_t)stream, scene, d_motion);
+}
+
+int lrt_temporal_accumulate_moving_host(const lrt_temporal_desc* desc, const lrt_scene_motion* scene,
+                                        const float* color, const lrt_features* cur, const lrt_temporal_state* prev,
+                                        const lrt_temporal_state* next, float* color_std, float* motion) {
+    RoctxRange rr_("lrt_temporal_accumulate_moving_host");
+    if (int rc = validate_temporal(desc, color, cur, prev, next, color_std)) return rc;
+    if (int rc = validate_motion(desc, scene, color, cur, prev, next, color_std, motion)) return rc;
+    return temporal_host(desc, color, cur, prev, next, color_std, scene, motion);
 }
 
 }  // extern "C"

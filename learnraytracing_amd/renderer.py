@@ -499,9 +499,99 @@ def temporal_accumulate_tensor(color, cur: dict, prev: Optional[dict], camera: L
                           out, n, check, lambda t: t.data_ptr(), make, (ctypes.c_void_p(s.cuda_stream),))
 
 
+def _sphere_array(spheres, what):
+    """A scene as a ctypes Sphere array: a sequence of Sphere structs, or floats [count, 4]
+    (centre, radius)."""
+    if isinstance(spheres, ctypes.Array) and spheres._type_ is L.Sphere:
+        return spheres
+    if len(spheres) < 1:
+        raise L.LrtError(L.LRT_E_INVALID, f"{what} is empty")
+    if isinstance(spheres, np.ndarray) or (len(spheres) and not isinstance(spheres[0], L.Sphere)):
+        a = np.ascontiguousarray(spheres, np.float32)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be Sphere structs or floats [count, 4]")
+        return (L.Sphere * max(len(a), 1)).from_buffer_copy(a.tobytes() if len(a) else bytes(16))
+    return (L.Sphere * max(len(spheres), 1))(*spheres)
+
+
+def _scene_motion(spheres, prev_spheres) -> L.SceneMotion:
+    """lrt_scene_motion of two scenes of the same spheres in the same order (it keeps them alive)."""
+    n = len(spheres)
+    if prev_spheres is None or len(prev_spheres) != n:
+        raise L.LrtError(L.LRT_E_INVALID, "spheres and prev_spheres differ in length")
+    sm = L.SceneMotion()
+    sm._arrays = (_sphere_array(spheres, "spheres"), _sphere_array(prev_spheres, "prev_spheres"))
+    sm.spheres = ctypes.cast(sm._arrays[0], ctypes.POINTER(L.Sphere))
+    sm.prev_spheres = ctypes.cast(sm._arrays[1], ctypes.POINTER(L.Sphere))
+    sm.count = n
+    return sm
+
+
+def temporal_accumulate_moving_host(color: np.ndarray, cur: dict, prev: Optional[dict], camera: L.Camera,
+                                    prev_camera: Optional[L.Camera], spheres, prev_spheres,
+                                    out: Optional[dict] = None, motion: Optional[np.ndarray] = None,
+                                    **params) -> dict:
+    """temporal_accumulate_host under moving spheres (lrt_temporal_accumulate_moving_host).
+    spheres: the scene the current frame was rendered with, prev_spheres: the scene of the frame
+    behind `prev` -- Sphere structs or floats [count, 4], the same spheres in the same order.
+    motion: a float32 [height, width, 4] buffer for the motion vectors (x, y: previous minus current
+    position in pixels; z: the matched sphere or -1; w: 1 if projectable), or None for none."""
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = temporal_desc(w, h, camera, prev_camera, **params)
+    sm = _scene_motion(spheres, prev_spheres)
+    n = w * h * 4
+
+    def check(buf, what):
+        _check_host_buffer(buf, n)
+
+    if motion is not None:
+        check(motion, "motion")
+    mp = ctypes.c_void_p(motion.ctypes.data) if motion is not None else None
+    return _temporal_call(lambda *a: L.lib().lrt_temporal_accumulate_moving_host(ctypes.byref(d), ctypes.byref(sm), *a),
+                          color, cur, prev, out, n, check, lambda b: b.ctypes.data,
+                          lambda: np.zeros((h, w, 4), np.float32), (mp,))
+
+
+def temporal_accumulate_moving_tensor(color, cur: dict, prev: Optional[dict], camera: L.Camera,
+                                      prev_camera: Optional[L.Camera], spheres, prev_spheres,
+                                      out: Optional[dict] = None, motion=None, stream=None, **params) -> dict:
+    """temporal_accumulate_moving_host on cuda float32 tensors (lrt_temporal_accumulate_moving_device):
+    asynchronous on `stream` and ordered only against it; the sphere arrays are read before it
+    returns. motion: a cuda tensor [height, width, 4], or None."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = temporal_desc(w, h, camera, prev_camera, **params)
+    sm = _scene_motion(spheres, prev_spheres)
+    n = w * h * 4
+    if not getattr(color, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color.device)
+
+    def check(t, what):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == torch.float32
+                and t.is_contiguous() and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda float32 tensor of >= {n} elements")
+
+    def make():
+        with torch.cuda.stream(s):
+            return torch.zeros((h, w, 4), device=color.device)
+
+    if motion is not None:
+        check(motion, "motion")
+    mp = ctypes.c_void_p(motion.data_ptr()) if motion is not None else None
+    return _temporal_call(lambda *a: L.lib().lrt_temporal_accumulate_moving_device(ctypes.byref(d), ctypes.byref(sm),
+                                                                                   *a),
+                          color, cur, prev, out, n, check, lambda t: t.data_ptr(), make,
+                          (mp, ctypes.c_void_p(s.cuda_stream)))
+
+
 class TemporalAccumulator:
-    """The two ping-pong states of a width x height frame on `device` and the previous camera:
-    step() blends a freshly rendered frame into the history and returns what the denoiser takes."""
+    """The two ping-pong states of a width x height frame on `device`, the previous camera and, for
+    a scene whose spheres move, the previous step's spheres: step() blends a freshly rendered frame
+    into the history and returns what the denoiser takes."""
 
     def __init__(self, width: int, height: int, device="cuda:0"):
         import torch
@@ -515,17 +605,24 @@ class TemporalAccumulator:
                         for _ in range(2)]
         self._cur = 0            # the state the last step wrote
         self._camera = None      # its camera (None: no history)
+        self._spheres = None     # its scene, if it was given one
 
     def reset(self) -> None:
         """Drop the history: the next step starts over (a new scene, a camera cut)."""
         self._camera = None
+        self._spheres = None
 
-    def step(self, color, features: dict, camera: L.Camera, cur_scale: float = 1.0, stream=None, **params):
+    def step(self, color, features: dict, camera: L.Camera, cur_scale: float = 1.0, stream=None, spheres=None,
+             motion=None, **params):
         """One accumulation step (temporal_accumulate_tensor) of the frame `color` with its
         features {"normal", "world_pos"[, "albedo"]} seen from `camera`. Returns (color, guides):
         the accumulated frame and the dict denoise_tensor takes ("normal", "world_pos", "albedo"
         if given, "color_std"); both are the accumulator's own tensors, valid until the step after
-        the next."""
+        the next. spheres: the scene the frame was rendered with (Sphere structs or floats
+        [count, 4]) where spheres move between steps: the step is then
+        temporal_accumulate_moving_tensor against the previous step's scene (on the first step, after
+        reset() and after a step without spheres the scene is its own predecessor), and `motion`, a
+        cuda tensor [height, width, 4], receives the motion vectors."""
         cur = {k: v for k, v in features.items() if k in L.TEMPORAL_CUR_NAMES}
         unknown = [k for k in features if k not in L.FEATURE_NAMES]
         if unknown:
@@ -535,8 +632,19 @@ class TemporalAccumulator:
         prev = None
         if self._camera is not None:
             prev = {k: v for k, v in self._states[self._cur].items() if k != "color_std"}
-        temporal_accumulate_tensor(color, cur, prev, camera, self._camera, out=out, stream=stream,
-                                   width=self.width, height=self.height, cur_scale=cur_scale, **params)
+        if spheres is None:
+            if motion is not None:
+                raise L.LrtError(L.LRT_E_INVALID, "motion needs spheres")
+            temporal_accumulate_tensor(color, cur, prev, camera, self._camera, out=out, stream=stream,
+                                       width=self.width, height=self.height, cur_scale=cur_scale, **params)
+            self._spheres = None
+        else:
+            scene = _sphere_array(spheres, "spheres")
+            before = self._spheres if self._spheres is not None and len(self._spheres) == len(scene) else scene
+            temporal_accumulate_moving_tensor(color, cur, prev, camera, self._camera, scene, before, out=out,
+                                              motion=motion, stream=stream, width=self.width, height=self.height,
+                                              cur_scale=cur_scale, **params)
+            self._spheres = (L.Sphere * len(scene)).from_buffer_copy(scene)
         self._cur = 1 - self._cur
         self._camera = L.Camera.from_buffer_copy(camera)
         return nxt["color"], {k: nxt[k] for k in L.GUIDE_NAMES if k in out}

@@ -12,7 +12,13 @@ output buffer once -- against which the same session's device-to-device copy mov
 (reads plus writes) is the yardstick; render_4spp_ms (the plain 4 spp render of the frame) and
 denoise_ms (the 5-pass denoise of the accumulated frame) are there for scale.
 
-  python tools/temporal_bench.py [--width W --height H --reps N --dtheta RAD] [--images DIR]
+  python tools/temporal_bench.py [--width W --height H --reps N --dtheta RAD] [--moving] [--images DIR]
+
+--moving adds the step under moving spheres (lrt_temporal_accumulate_moving_device) on the same
+camera pair: moving_step_ms (the default scene, one sphere translated between the two frames, no
+motion output), moving_step_motion_ms (with it), moving_step_1000_ms (random_scene(1000, 1), no
+motion output) and moving_over_static = moving_step_ms / step_ms. Without the flag the line is the
+one it always was.
 """
 import argparse
 import json
@@ -28,6 +34,10 @@ sys.path.insert(0, ROOT)
 
 HOLD_SECONDS = 0.025
 CUR = ("normal", "world_pos", "albedo")
+# --moving: the step under moving spheres, one sphere translated by MOVING_STEP between the two
+# frames -- the default scene without and with motion vectors, and random_scene(1000, 1) without
+MOVING_FIELDS = ("moving_step_ms", "moving_step_motion_ms", "moving_step_1000_ms")
+MOVING_STEP = 0.1
 
 
 def step_bytes(albedo=True, color_std=True):
@@ -71,6 +81,8 @@ def main(argv=None):
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--dtheta", type=float, default=0.02, help="the orbit step between the two cameras (rad)")
     ap.add_argument("--reps", type=int, default=40, help="timed repetitions (>= 20)")
+    ap.add_argument("--moving", action="store_true",
+                    help="also time lrt_temporal_accumulate_moving_device (the MOVING_FIELDS of the line)")
     ap.add_argument("--images", metavar="DIR",
                     help="write the 1 spp, accumulated and accumulated-then-denoised frames of 16 orbit steps there")
     args = ap.parse_args(argv)
@@ -149,6 +161,39 @@ def main(argv=None):
             "denoise_ms": round(t_den["median"], 4), "denoise_ms_spread": rnd(t_den),
             "version": L.lib().lrt_version().decode(),
         }
+        if args.moving:
+            motion = frame()
+
+            def moving_leg(spheres, mats, moved, with_motion):
+                """Median ms of the moving step on the scene `spheres` whose sphere `moved` came
+                MOVING_STEP along x: the previous state is the previous scene's frame from cam0."""
+                before = list(spheres)
+                c = before[moved].center
+                before[moved] = L.Sphere(L.f3(c.x - MOVING_STEP, c.y, c.z), before[moved].radius)
+                lrt.set_scene(before, mats)
+                b0, f0 = render(cam0, 0)
+                lrt.set_scene(spheres, mats)
+                b1, f1 = render(cam1, 1)
+                st = lrt.temporal_accumulate_tensor(b0, f0, None, cam0, stream=s, cur_scale=1.0)
+                pv = {n: st[n] for n in L.TEMPORAL_STATE_NAMES}
+                s.synchronize()
+                return timed(torch, s, lambda: lrt.temporal_accumulate_moving_tensor(
+                    b1, f1, pv, cam1, cam0, spheres, before, out=nxt, motion=motion if with_motion else None,
+                    stream=s, cur_scale=2.0), args.reps)
+
+            sph9, mat9 = lrt.default_scene()
+            sph1000, mat1000 = lrt.random_scene(1000, 1)
+            try:
+                t_mov = moving_leg(sph9, mat9, 2, False)
+                t_mot = moving_leg(sph9, mat9, 2, True)
+                t_1000 = moving_leg(sph1000, mat1000, 500, False)
+            finally:
+                lrt.set_scene(sph9, mat9)
+            s.synchronize()
+            for name, t in zip(MOVING_FIELDS, (t_mov, t_mot, t_1000)):
+                line[name] = round(t["median"], 4)
+                line[name + "_spread"] = rnd(t)
+            line["moving_over_static"] = round(t_mov["median"] / t_step["median"], 3)
         if args.images:
             os.makedirs(args.images, exist_ok=True)
             steps = 16
