@@ -21,6 +21,24 @@ int lrt_libm_eval_host(int kind, const float* in, float* out, long long n);
 /* Device evaluation of the same restatement (device pointers, blocking). */
 int lrt_libm_eval_device(int kind, const float* d_in, float* d_out, long long n);
 
+/* The short exact divisions of the Lambert light sample (lrt_trace.h: div_pi, member_quot and the
+ * bare sequences div_pi_fast, div_by_rcp) against the plain IEEE divisions, over cases
+ * [first, first + count) of sweep `what`, by the functions the kernels call:
+ *   0: x / kPI, case = x's bit pattern (2^32 cases);
+ *   1: v / l for every float l of [0.5, 2] (2^24 + 1 divisors) times 32 dividend patterns (the
+ *      edges 2^-96 and 2^96 of the short form's range, values around 1 and l, both signs, +-0,
+ *      denormal and tiny dividends, random ones), case = 32 * divisor index + pattern;
+ *   2: random (l, v) pairs inside the short form's range, case = the pair's seed (< 2^40);
+ *   3: as 1 for divisors of any bit pattern (zero, denormal, negative, huge, inf, NaN), hashed
+ *      from the case number: the fallback to the plain divisions.
+ * out[0]: cases where the complete function (range test and fallback included) differs from the
+ * division; out[1]: cases inside the stated range where the bare sequence differs; out[2]: cases
+ * inside that range; out[3]: the lowest failing case (all ones: none). All of out[0], out[1]
+ * must be 0. on_device = 0: the host build of the sequences (hardware fma where the CPU has
+ * it, several threads); otherwise one launch on the current device. Blocking. */
+int lrt_exact_div_sweep(int what, unsigned long long first, unsigned long long count, int on_device,
+                        unsigned long long* out);
+
 /* BVH diagnostics (host only, no GPU): build the BVH of the given scene and trace n rays
  * (6 floats each: origin, direction) with the device traversal code. out[7]: mean nodes
  * visited, mean spheres tested, max nodes, max spheres, mismatches per ray against the

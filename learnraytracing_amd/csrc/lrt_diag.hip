@@ -4,6 +4,8 @@
 #include "lrt_grid_build.h"
 #include "lrt_internal.h"
 
+#include <thread>
+
 namespace lrt {
 
 LRT_HD float libm_eval(int kind, float x) {
@@ -31,6 +33,101 @@ __global__ void libm_kernel(int kind, const float* __restrict__ in, float* __res
     out[i] = libm_eval(kind, x);
 }
 
+
+// ---- lrt_exact_div_sweep: the short exact divisions (lrt_trace.h) against the plain ones -----
+// One case of sweep `what`; c[0]: full-function mismatches, c[1]: mismatches of the bare
+// sequence inside its stated range, c[2]: cases inside that range, c[3]: lowest failing index.
+LRT_HD bool same_bits(float a, float b) { return libm::f2u(a) == libm::f2u(b) || (a != a && b != b); }
+LRT_HD uint32_t sweep_hash(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return x;
+}
+constexpr int kSweepDividends = 32;
+// dividend pattern p for divisor l (case key k): the edges of div_by_rcp's range, values around
+// 1 and l, operands outside the range (zeros, denormals, tiny: the fallback's), random ones
+LRT_HD float sweep_dividend(int p, float l, uint32_t k) {
+    const uint32_t lb = libm::f2u(l);
+    const uint32_t fixed[20] = {0x0f800000u, 0x0f800001u, 0x6f800000u, 0x6f7fffffu,   // 2^-96, 2^96 and next inside
+                                0x3f800000u, 0x3f7fffffu, 0x3f800001u, 0x40000000u, 0x3f000000u, 0x3fffffffu,
+                                lb, lb - 1u, lb + 1u, 0x8f800000u, 0xef800000u,
+                                0x00000000u, 0x80000000u, 0x00000001u, 0x0f7fffffu, 0x80800000u};   // outside
+    if (p < 20) return libm::u2f(fixed[p]);
+    const uint32_t h = sweep_hash(k * (uint32_t)kSweepDividends + (uint32_t)p);
+    const uint32_t e = 31u + (sweep_hash(h) % 192u);   // biased exponents 31..222: [2^-96, 2^96)
+    return libm::u2f((h & 0x807fffffu) | (e << 23));
+}
+LRT_HD void sweep_member(float l, uint32_t k, int p, unsigned long long idx, unsigned long long* c) {
+    const F3 v = f3(sweep_dividend(p, l, k), sweep_dividend((p + 1) % kSweepDividends, l, k),
+                    sweep_dividend((p + 7) % kSweepDividends, l, k));
+    const F3 q = member_quot(v, l);
+    if (!same_bits(q.x, v.x / l) || !same_bits(q.y, v.y / l) || !same_bits(q.z, v.z / l)) {
+        ++c[0];
+        c[3] = idx < c[3] ? idx : c[3];
+    }
+    const float a = __builtin_fabsf(v.x);
+    if (libm::f2u(l) - 0x3f000000u <= 0x01000000u && a >= 0x1p-96f && a <= 0x1p96f) {
+        ++c[2];
+        if (!same_bits(div_by_rcp(v.x, l, rcp_fast(l)), v.x / l)) {
+            ++c[1];
+            c[3] = idx < c[3] ? idx : c[3];
+        }
+    }
+}
+LRT_HD void exact_div_case(int what, unsigned long long idx, unsigned long long* c) {
+    if (what == 0) {   // x / kPI over bit patterns
+        const float x = libm::u2f((uint32_t)idx);
+        const float ref = x / kPI;
+        if (!same_bits(div_pi(x), ref)) {
+            ++c[0];
+            c[3] = idx < c[3] ? idx : c[3];
+        }
+        if (div_pi_in_range(x)) {
+            ++c[2];
+            if (!same_bits(div_pi_fast(x), ref)) {
+                ++c[1];
+                c[3] = idx < c[3] ? idx : c[3];
+            }
+        }
+    } else if (what == 1) {   // every divisor of [0.5, 2] against each dividend pattern
+        const uint32_t j = (uint32_t)(idx / kSweepDividends);
+        sweep_member(libm::u2f(0x3f000000u + j), j, (int)(idx % kSweepDividends), idx, c);
+    } else if (what == 2) {   // random pairs inside the range
+        const uint32_t h = sweep_hash((uint32_t)idx * 2u + 0x9E3779B9u * (uint32_t)(idx >> 32));
+        sweep_member(libm::u2f(0x3f000000u + (h & 0x00ffffffu)), sweep_hash(h + 1u), 20 + (int)(h >> 24) % 12, idx, c);
+    } else {   // any divisor bit pattern (the fallback: zero, denormal, negative, huge, inf, NaN divisors)
+        const uint32_t h = sweep_hash((uint32_t)idx);
+        sweep_member(libm::u2f(h), h, (int)(idx % kSweepDividends), idx, c);
+    }
+}
+LRT_HD void exact_div_span(int what, unsigned long long first, unsigned long long end, unsigned long long step,
+                           unsigned long long* c) {
+    for (unsigned long long i = first; i < end; i += step) exact_div_case(what, i, c);
+}
+// the host with hardware fma where the CPU has it (the sequences are three to five fmas a case)
+__attribute__((target("fma"))) static void exact_div_span_fma(int what, unsigned long long first, unsigned long long end,
+                                                              unsigned long long* c) {
+    exact_div_span(what, first, end, 1, c);
+}
+__global__ __launch_bounds__(256) void exact_div_kernel(int what, unsigned long long first, unsigned long long end,
+                                                        unsigned long long* out) {
+    unsigned long long c[4] = {0, 0, 0, ~0ull};
+    const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+    // whole waves enter each trip, so the sequences' ballots see full waves (trailing lanes clamp)
+    for (unsigned long long i = first + (unsigned long long)blockIdx.x * blockDim.x; i < end; i += step) {
+        const unsigned long long k = i + threadIdx.x;
+        unsigned long long t[4] = {0, 0, 0, ~0ull};
+        exact_div_case(what, k < end ? k : end - 1, t);
+        if (k < end) {
+            c[0] += t[0];
+            c[1] += t[1];
+            c[2] += t[2];
+            c[3] = t[3] < c[3] ? t[3] : c[3];
+        }
+    }
+    for (int k = 0; k < 3; ++k)
+        if (c[k]) atomicAdd(&out[k], c[k]);
+    if (c[3] != ~0ull) atomicMin(&out[3], c[3]);
+}
 
 // lrt_scatter_eval's case i: Scatter (lrt_trace.h, parallel.cpp:78-196) of material ids[i]
 // for the ray rays[6i..] (through the Ray ctor) at the hit recs[7i..] under RNG state seeds[i].
@@ -446,6 +543,58 @@ int lrt_libm_eval_device(int kind, const float* d_in, float* d_out, long long n)
     libm_kernel<<<(unsigned)((n + 255) / 256), 256, 0, nullptr>>>(kind, d_in, d_out, n);
     LRT_HIP(hipGetLastError());
     LRT_HIP(hipDeviceSynchronize());
+    return LRT_OK;
+}
+
+
+int lrt_exact_div_sweep(int what, unsigned long long first, unsigned long long count, int on_device,
+                        unsigned long long* out) {
+    const unsigned long long limit = what == 0   ? 1ull << 32
+                                     : what == 1 ? ((1ull << 24) + 1) * kSweepDividends
+                                                 : 1ull << 40;
+    if (what < 0 || what > 3 || !out || first > limit || count > limit - first)
+        return fail(LRT_E_INVALID, "exact div sweep: invalid arguments");
+    out[0] = out[1] = out[2] = 0;
+    out[3] = ~0ull;
+    if (count == 0) return LRT_OK;
+    const unsigned long long end = first + count;
+    if (on_device) {
+        unsigned long long* d = nullptr;
+        LRT_HIP(hipMalloc(&d, 4 * sizeof(unsigned long long)));
+        hipError_t e = hipMemcpy(d, out, 4 * sizeof(unsigned long long), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            const unsigned blocks = (unsigned)std::min<unsigned long long>((count + 255) / 256, 4096);
+            exact_div_kernel<<<blocks, 256>>>(what, first, end, d);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(out, d, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (e != hipSuccess) return fail(LRT_E_HIP, std::string("exact div sweep: ") + hipGetErrorString(e));
+        return LRT_OK;
+    }
+    const bool fma = __builtin_cpu_supports("fma");
+    const unsigned nt = (unsigned)std::min<unsigned long long>(
+        std::max(1u, std::min(std::thread::hardware_concurrency(), 16u)), (count + 65535) / 65536);
+    std::vector<unsigned long long> part(4 * (size_t)nt, 0);
+    std::vector<std::thread> th;
+    constexpr unsigned long long kChunk = 1ull << 20;   // dealt round-robin: the slow (denormal) cases spread out
+    for (unsigned t = 0; t < nt; ++t) {
+        unsigned long long* c = &part[4 * (size_t)t];
+        c[3] = ~0ull;
+        th.emplace_back([=] {
+            for (unsigned long long a = first + t * kChunk; a < end; a += nt * kChunk) {
+                const unsigned long long b = std::min(a + kChunk, end);
+                if (fma) exact_div_span_fma(what, a, b, c);
+                else exact_div_span(what, a, b, 1, c);
+            }
+        });
+    }
+    for (auto& x : th) x.join();
+    for (unsigned t = 0; t < nt; ++t) {
+        for (int k = 0; k < 3; ++k) out[k] += part[4 * (size_t)t + k];
+        out[3] = std::min(out[3], part[4 * (size_t)t + 3]);
+    }
     return LRT_OK;
 }
 

@@ -342,7 +342,10 @@ int pack_scene(const lrt_sphere* s, const lrt_material* m, int n, std::vector<fl
         float typef;
         memcpy(&typef, &type, 4);
         mats[3 * i + 0] = make_float4(m[i].albedo.x, m[i].albedo.y, m[i].albedo.z, typef);
-        mats[3 * i + 1] = make_float4(m[i].emissive.x, m[i].emissive.y, m[i].emissive.z, m[i].roughness);
+        // row 1's w: Metal's roughness; no other type reads it, and a Dielectric's carries its
+        // schlick r0 (lrt_trace.h), the same two IEEE operations done once here
+        mats[3 * i + 1] = make_float4(m[i].emissive.x, m[i].emissive.y, m[i].emissive.z,
+                                      diel ? schlick_r0(m[i].ri) : m[i].roughness);
         mats[3 * i + 2] = diel ? make_float4(1.0f, 1.0f, 1.0f, m[i].ri)
                                : make_float4(m[i].albedo.x, m[i].albedo.y, m[i].albedo.z, m[i].ri);
         // parallel.cpp:96: skip only if every channel <= 0

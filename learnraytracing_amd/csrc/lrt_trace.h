@@ -93,6 +93,35 @@ LRT_DEV float rcp_rn(float x) {
 #endif
     return r;
 }
+// x / kPI, the constant divisor of the Lambert light sample (parallel.cpp:129), without the
+// generic division: with c = RN(1 / kPI), q = x * c is within a few ulps of the quotient, the
+// residual r = fma(-q, kPI, x) is exact, and fma(r, c, q) rounds to x / kPI. Equal to the
+// division for x = +0 and every float in [2^-104, FLT_MAX] (every bit pattern swept on the
+// host, tests/test_exact_div.py, and on gfx950, tools/fpexact.hip). Below 2^-104 the residual
+// falls among the denormals and stops being exact, -0 comes out as +0 and infinity as NaN,
+// and the path's operand max(0, l.nl) * omega is never negative: all of those (and NaN) take
+// the division, wave-uniformly on the device like sqrt_rn. One unsigned compare of the bit
+// pattern covers the range, as in rsqrt_len; +0 is the common operand (a light below the
+// horizon) and is tested beside it.
+constexpr float kRcpPI = 1.0f / kPI;
+LRT_DEV float div_pi_fast(float x) {
+    float q = x * kRcpPI;
+    const float r = __builtin_fmaf(-q, kPI, x);
+    return __builtin_fmaf(r, kRcpPI, q);
+}
+LRT_DEV bool div_pi_in_range(float x) {
+    const uint32_t u = libm::f2u(x);
+    return u - 0x0b800000u <= 0x7f7fffffu - 0x0b800000u || u == 0u;
+}
+LRT_DEV float div_pi(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float q = div_pi_fast(x);
+    if (__builtin_expect(__ballot(!div_pi_in_range(x)) != 0, 0)) q = x / kPI;
+    return q;
+#else
+    return div_pi_in_range(x) ? div_pi_fast(x) : x / kPI;
+#endif
+}
 LRT_DEV float length(F3 v) { return sqrt_rn(v.x * v.x + v.y * v.y + v.z * v.z); } // maths.h:15
 // rcp_rn(sqrt_rn(d)), normalize's factor, with ONE range check for both steps: for a finite
 // d >= 2^-96 the root is the fast sequence's, and it lies in [2^-48, 2^64], inside rcp_rn's
@@ -129,7 +158,47 @@ LRT_DEV void renorm_lut_fill(float* lut, int tid, int block) {
     }
 }
 constexpr int kPowTableBytes = 16 * 8 + 16 * 8 + 32 * 8;   // powf tables (lrt_libm.h) staged in LDS
-LRT_DEV F3 normalize_member(F3 v) { float l = length(v); return f3(v.x / l, v.y / l, v.z / l); } // maths.h:19
+// v / l for a divisor whose correctly rounded reciprocal r = RN(1 / l) is at hand: q = v * r is
+// within 2 ulps, and two residual corrections q += fma(-q, l, v) * r reach the correctly rounded
+// quotient (the second is Markstein's step: a faithful q, an exact residual, a correctly rounded
+// r). This is LLVM's own division sequence without v_div_scale's scaling and v_div_fixup.
+// Valid for l in [0.5, 2] and 2^-96 <= |v| <= 2^96: there q is normal and each residual, about
+// 2^-24 |v|, is a normal float too, so both fmas are exact where the argument needs them; every
+// significand of l in that range against dividends at the edges and across the range, and 2^30
+// random pairs, on the host (tests/test_exact_div.py) and on gfx950 (tools/fpexact.hip).
+// Not valid for a zero dividend: -0 / l is -0, the short form gives +0 (fma(+0, r, -0)).
+LRT_DEV float div_by_rcp(float v, float l, float r) {
+    float q = v * r;
+    float e = __builtin_fmaf(-q, l, v);
+    q = __builtin_fmaf(e, r, q);
+    e = __builtin_fmaf(-q, l, v);
+    return __builtin_fmaf(e, r, q);
+}
+// v / l for the three components of v with one reciprocal: rcp_fast(l) is RN(1 / l) for every l
+// in div_by_rcp's range (above: |l| in [2^-125, 2^125]; the host divides). The range test is one
+// unsigned compare of l's bit pattern (NaN and negatives lie outside) and the lower bound on the
+// smallest |component|. The upper bound 2^96 is the caller's: normalize_member's l = length(v)
+// in [0.5, 2] holds every |component| below 2 (1 + 2^-22). A lane outside the range sends the
+// wave through the three plain divisions.
+LRT_DEV bool member_quot_in_range(F3 v, float l) {
+    const float lo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), __builtin_fabsf(v.z));
+    return libm::f2u(l) - 0x3f000000u <= 0x40000000u - 0x3f000000u && lo >= 0x1p-96f;
+}
+LRT_DEV F3 member_quot(F3 v, float l) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (!member_quot_in_range(v, l)) return f3(v.x / l, v.y / l, v.z / l);
+#endif
+    const float r = rcp_fast(l);
+    F3 q = f3(div_by_rcp(v.x, l, r), div_by_rcp(v.y, l, r), div_by_rcp(v.z, l, r));
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_expect(__ballot(!member_quot_in_range(v, l)) != 0, 0)) q = f3(v.x / l, v.y / l, v.z / l);
+#endif
+    return q;
+}
+// maths.h:19, f3(v.x / l, v.y / l, v.z / l). Its one caller, the Lambert light sample's
+// l = su cos sin + sv sin sin + sw cos, has length 1 to a few ulps, so the range test is
+// essentially never failed.
+LRT_DEV F3 normalize_member(F3 v) { return member_quot(v, length(v)); }
 LRT_DEV F3 reflect(F3 v, F3 n) { return v + 2.0f * (-dot(v, n) * n); }             // maths.h:100-103
 LRT_DEV bool refract(F3 v, F3 n, float nint, F3& out) {                             // maths.h:106-118
     float dt = dot(v, n);
@@ -140,10 +209,18 @@ LRT_DEV bool refract(F3 v, F3 n, float nint, F3& out) {                         
     }
     return false;
 }
-LRT_DEV float schlick(float cosine, float ri, const libm::PowTables& T) {          // maths.h:122-127
+// schlick's r0 depends on the material alone: pack_scene evaluates it once per Dielectric, with
+// these very operations (IEEE on the host, contraction off), into the material row float a
+// Dielectric does not otherwise use (the roughness slot), and the kernels read it there.
+LRT_DEV float schlick_r0(float ri) {                                                // maths.h:124-125
     float r0 = (1.0f - ri) / (1.0f + ri);
-    r0 = r0 * r0;
+    return r0 * r0;
+}
+LRT_DEV float schlick_with_r0(float cosine, float r0, const libm::PowTables& T) {  // maths.h:126
     return r0 + (1.0f - r0) * libm::powf5(1.0f - cosine, T);
+}
+LRT_DEV float schlick(float cosine, float ri, const libm::PowTables& T) {          // maths.h:122-127
+    return schlick_with_r0(cosine, schlick_r0(ri), T);
 }
 LRT_DEV float schlick(float cosine, float ri) { return schlick(cosine, ri, libm::pow_tables()); }
 
@@ -213,13 +290,14 @@ LRT_DEV F3 RandomInUnitSphere(uint32_t& s) {
 // squared (maths.cpp:59, parallel.cpp:109), so r*r is folded once on the host.
 // Material: three float4 rows: (albedo.xyz, type), (emissive.xyz, roughness),
 // (attenuation.xyz, ri) where attenuation = albedo (Lambert, Metal) or 1 (Dielectric,
-// parallel.cpp:90,144,192).
+// parallel.cpp:90,144,192). Only Metal reads its roughness (parallel.cpp:137-148), so a
+// Dielectric's row carries schlick_r0(ri) in that float instead (pack_scene).
 struct Material {
     F3 albedo;
     int type;
     int id;   // the table index: the reference's `&mat == &smat` self test (parallel.cpp:98)
     F3 emissive;
-    float roughness;
+    float roughness;   // Dielectric: schlick_r0(ri)
     F3 att;
     float ri;
 };
@@ -464,7 +542,7 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
                 float mx = (0.0f < d) ? d : 0.0f;   // std::max(0.0f, d)
                 const float4 e = sc.mats[3 * i + 1];
                 defer->l = renormalize(l, sc.rnlut);   // the shadow Ray's ctor normalises again (maths.h:133-137)
-                defer->contrib = (mat.albedo * f3(e.x, e.y, e.z)) * (mx * omega / kPI);
+                defer->contrib = (mat.albedo * f3(e.x, e.y, e.z)) * div_pi(mx * omega);   // mx * omega / kPI
                 defer->li = i;
                 defer->on = true;
                 continue;
@@ -492,7 +570,7 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
                 float d = dot(l, nl);
                 float mx = (0.0f < d) ? d : 0.0f;   // std::max(0.0f, d)
                 const float4 e = sc.mats[3 * i + 1];
-                outLightE = outLightE + (mat.albedo * f3(e.x, e.y, e.z)) * (mx * omega / kPI);
+                outLightE = outLightE + (mat.albedo * f3(e.x, e.y, e.z)) * div_pi(mx * omega);   // mx * omega / kPI
             }
         }
         return X;
@@ -520,7 +598,7 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
         cosine = -dot(rdir, rec.normal);
     }
     if (refract(rdir, outwardN, nint, refr))
-        reflProb = schlick(cosine, mat.ri, sc.pow);
+        reflProb = schlick_with_r0(cosine, mat.roughness, sc.pow);   // the row's r0 = schlick_r0(mat.ri)
     else
         reflProb = 1.0f;
     return RandomFloat01(rng) < reflProb ? refl : refr;

@@ -2,9 +2,10 @@
 // sequences against the correctly rounded IEEE results the build uses today
 // (__builtin_sqrtf and '/', which LLVM expands into the full correction sequences).
 //
-//   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -o tools/fpexact tools/fpexact.hip
+//   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -Iinclude -o tools/fpexact tools/fpexact.hip
 //   tools/fpexact            # all 2^31 non-negative floats for the unary functions,
-//                            # 2^32 random pairs per range for the divisions
+//                            # 2^32 random pairs per range for the divisions, all 2^32
+//                            # patterns for the product's div_pi / member_quot sweep
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -103,6 +104,30 @@ __global__ void div_kernel(uint32_t seed, int emin, int emax, unsigned long long
     if (a * rcp_nr(b) != ref) atomicAdd(&cnt[2], 1ull);
 }
 
+// the product's short divisions (lrt_trace.h): div_pi over every bit pattern; member_quot for every
+// divisor l of [0.5, 2] (base + thread) against dividends hashed over [2^-96, 2^96), both signs,
+// plus the range's edges. cnt[0]: div_pi, cnt[1]: div_pi_fast inside its range, cnt[2]:
+// member_quot, cnt[3]: div_by_rcp alone
+__global__ void shortdiv_kernel(uint32_t base, unsigned long long* cnt) {
+    const uint32_t u = base + blockIdx.x * blockDim.x + threadIdx.x;
+    const float x = __uint_as_float(u);
+    if (!same(lrt::div_pi(x), x / lrt::kPI)) atomicAdd(&cnt[0], 1ull);
+    if (lrt::div_pi_in_range(x) && !same(lrt::div_pi_fast(x), x / lrt::kPI)) atomicAdd(&cnt[1], 1ull);
+    const uint32_t j = u & 0x01ffffffu;   // 2^25 divisor slots, 128 rounds of dividends each
+    if (j > 0x01000000u) return;
+    const float l = __uint_as_float(0x3f000000u + j);
+    const uint32_t edges[4] = {0x0f800000u, 0x6f800000u, 0x8f800000u, 0xef800000u};   // +-2^-96, +-2^96
+    float v[3];
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t h = hash(u * 3u + (uint32_t)k);
+        v[k] = (h >> 28) == 0 ? __uint_as_float(edges[(h >> 26) & 3u])
+                              : __uint_as_float((h & 0x807fffffu) | ((31u + (h >> 8) % 192u) << 23));
+    }
+    const lrt::F3 q = lrt::member_quot(lrt::f3(v[0], v[1], v[2]), l);
+    if (!same(q.x, v[0] / l) || !same(q.y, v[1] / l) || !same(q.z, v[2] / l)) atomicAdd(&cnt[2], 1ull);
+    if (!same(lrt::div_by_rcp(v[0], l, lrt::rcp_fast(l)), v[0] / l)) atomicAdd(&cnt[3], 1ull);
+}
+
 int main() {
     unsigned long long* d;
     const size_t n = kNUnary * 256 + 8;
@@ -138,6 +163,18 @@ int main() {
         int lo = -1, hi = -1;
         for (int e = 0; e < 256; ++e) if (hc[2 + e]) { t += hc[2 + e]; if (lo < 0) lo = e; hi = e; }
         printf("rcp_nr2 (|x| in [2^-126, 2^127)) mismatches %llu (biased exponents %d..%d)\n", t, lo, hi);
+    }
+    {
+        unsigned long long* c = d;
+        hipMemset(c, 0, 4 * 8);
+        for (uint64_t base = 0; base < 0x100000000ull; base += 1ull << 28)
+            shortdiv_kernel<<<(1u << 28) / 256, 256>>>((uint32_t)base, c);
+        unsigned long long hc[4];
+        hipMemcpy(hc, c, sizeof(hc), hipMemcpyDeviceToHost);
+        printf("product div_pi vs x / kPI over all 2^32 patterns: %llu mismatches (bare sequence in its range: %llu)\n",
+               hc[0], hc[1]);
+        printf("product member_quot vs v / l, every l of [0.5, 2] x 128 dividend triples: %llu mismatches "
+               "(div_by_rcp alone: %llu)\n", hc[2], hc[3]);
     }
     const int ranges[][2] = {{-20, 20}, {-60, 60}, {-1, 1}, {-126, 127}};
     for (auto& r : ranges) {
