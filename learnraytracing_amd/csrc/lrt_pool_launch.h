@@ -129,8 +129,11 @@ int launch_pool(KernelArgs a, bool lds, int xc, int rows, hipStream_t s) {
     // the split tail: the last split16/16 of the (heaviest-first) tiles served as halves, in
     // launches of few tiles per wave (a.lateFetch) that give every queue a block (the halves are
     // extra queue items: a queue without a block would leave them undone); a recording launch
-    // times whole tiles
-    const bool split = !a.tcost && wpb == 1 && a.lateFetch && blocks >= kV0Queues;
+    // times whole tiles. Only the instances that serve halves (pool_kernel's kSplit: depth <= 8,
+    // linear scan, one-wave blocks, tiles two or more pixels wide) are given a tail; the others
+    // ignore the value, and lrt_last_launch() reports split_from == tasks for them
+    constexpr bool kHalves = TX >= 2 && MAXD <= 8;
+    const bool split = kHalves && acc == kAccScan && !a.tcost && wpb == 1 && a.lateFetch && blocks >= kV0Queues;
     // (the slim instance's 5,120 waves leave a launch alone 2.8 tiles per wave instead of 3.5: where
     // a split tail is asked for it takes a larger share, one stream 0.2392 -> 0.2355 ms at 8/16
     // against 5/16 (0.2349 at four waves), profiles/r8_occ)

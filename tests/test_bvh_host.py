@@ -79,6 +79,23 @@ def test_axis_aligned_and_surface_rays():
     assert stats(sph, np.array(rays, np.float32))[4] == 0.0
 
 
+def colinear_chain(n):
+    """n tiny spheres on a line, 0.01 apart: median splits recurse to the builder's depth cap."""
+    return [L.Sphere(L.f3(0.01 * i, 0.0, 0.0), 0.004) for i in range(n)]   # colinear, tiny
+
+
+def chain_rays(g, n, across=3000, along=100):
+    """`across` rays crossing colinear_chain(n) nearly at right angles, then `along` rays down its axis."""
+    o = np.zeros((across, 3))
+    o[:, 0] = g.uniform(-1, 0.01 * n + 1, across)
+    o[:, 1] = g.uniform(-0.01, 0.01, across)
+    o[:, 2] = -1.0
+    d = np.tile([0.0, 0.0, 1.0], (across, 1)) + g.normal(0, 0.002, (across, 3))
+    rays = np.concatenate([o, d], axis=1).astype(np.float32)
+    rays2 = np.concatenate([np.array([[-1.0, 0.0, 0.0]] * along), np.tile([1.0, 0.0, 0.0], (along, 1))], axis=1)
+    return np.concatenate([rays, rays2.astype(np.float32)])
+
+
 @pytest.mark.parametrize("n,leaf", [(4096, 1), (4096, 16), (1000, 2)])
 def test_stack_depth_bound_deepest_trees(monkeypatch, n, leaf):
     """The deepest trees the builder makes (leaf size 1: 4096 leaves; a colinear chain of
@@ -89,15 +106,7 @@ def test_stack_depth_bound_deepest_trees(monkeypatch, n, leaf):
     sph, _ = random_scene(n, 1)
     res = stats(sph, random_rays(g, 3000, [-6, -0.6, -7], [6, 3, 4]))
     assert res[4] == 0.0 and res[5] >= 1
-    chain = [L.Sphere(L.f3(0.01 * i, 0.0, 0.0), 0.004) for i in range(n)]   # colinear, tiny
-    o = np.zeros((3000, 3))
-    o[:, 0] = g.uniform(-1, 0.01 * n + 1, 3000)
-    o[:, 1] = g.uniform(-0.01, 0.01, 3000)
-    o[:, 2] = -1.0
-    d = np.tile([0.0, 0.0, 1.0], (3000, 1)) + g.normal(0, 0.002, (3000, 3))
-    rays = np.concatenate([o, d], axis=1).astype(np.float32)
-    rays2 = np.concatenate([np.array([[-1.0, 0.0, 0.0]] * 100), np.tile([1.0, 0.0, 0.0], (100, 1))], axis=1)
-    res = stats(chain, np.concatenate([rays, rays2.astype(np.float32)]))
+    res = stats(colinear_chain(n), chain_rays(g, n))
     assert res[4] == 0.0
 
 

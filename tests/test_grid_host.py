@@ -33,15 +33,25 @@ def test_random_scene_random_rays(n):
     assert res[1] < n / 4 or n < 100   # the walk tests few spheres
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 5, 9, 16])
+SMALL_SCENES = [1, 2, 3, 5, 9, 16]
+SMALL_BOX = ([-4, -0.6, -3], [4, 3, 3])   # the origins of the small scenes' rays
+
+
+def small_scene(n):
+    """The reference's own 9 spheres, or the first n of a tiny random scene."""
+    from learnraytracing_amd.scene import default_scene
+    sph = default_scene()[0] if n == 9 else random_scene(max(n, 2), 1)[0][:n]
+    assert len(sph) == n
+    return sph
+
+
+@pytest.mark.parametrize("n", SMALL_SCENES)
 def test_small_scenes(n):
     """Scenes at or below kBvhMinSpheres get the grid too (opt-in: LRT_F_GRID /
     LRT_ACCEL=grid): the reference's own 9 spheres (configs 1-3) and tiny random scenes."""
-    from learnraytracing_amd.scene import default_scene
     g = np.random.default_rng(40 + n)
-    sph = default_scene()[0] if n == 9 else random_scene(max(n, 2), 1)[0][:n]
-    assert len(sph) == n
-    res = gstats(sph, random_rays(g, 3000, [-4, -0.6, -3], [4, 3, 3]))
+    sph = small_scene(n)
+    res = gstats(sph, random_rays(g, 3000, *SMALL_BOX))
     assert res[3] == 0.0, res
     if n == 9:   # the ground alone is tested first; the 8 others are walked
         assert res[8] == 1.0 and res[1] < 5, res
@@ -73,20 +83,20 @@ def _cells(sph):
     return lo, hi, np.array(res[5:8], int)
 
 
-def test_axis_aligned_plane_and_corner_rays():
-    g = np.random.default_rng(11)
-    sph, _ = random_scene(1000, 1)
+def axis_plane_and_corner_rays(g, sph, per_axis=200, lattice=1500):
+    """Axis-aligned rays (per_axis for each of the six directions), then `lattice` rays from the
+    grid's (approximate) cell planes and corners."""
     lo, hi, n = _cells(sph)
     h = (hi - lo) / n
     rays = []
     for axis in range(3):
         for sgn in (1.0, -1.0):
-            for _ in range(200):
+            for _ in range(per_axis):
                 o = g.uniform(lo - 0.5, hi + 0.5)
                 d = np.zeros(3)
                 d[axis] = sgn
                 rays.append(np.concatenate([o, d]))
-    for _ in range(1500):   # origins on (approximate) cell planes and corners, any direction
+    for _ in range(lattice):   # origins on (approximate) cell planes and corners, any direction
         k = g.integers(0, n + 1)
         o = lo + k * h + g.choice([0.0, 1e-7, -1e-7], size=3)
         d = g.normal(size=3)
@@ -94,7 +104,31 @@ def test_axis_aligned_plane_and_corner_rays():
             k2 = g.integers(0, n + 1)
             d = lo + k2 * h - o + 1e-6
         rays.append(np.concatenate([o, d]))
-    assert gstats(sph, np.array(rays, np.float32))[3] == 0.0
+    return np.array(rays, np.float32)
+
+
+def test_axis_aligned_plane_and_corner_rays():
+    g = np.random.default_rng(11)
+    sph, _ = random_scene(1000, 1)
+    assert gstats(sph, axis_plane_and_corner_rays(g, sph))[3] == 0.0
+
+
+def grazing_and_surface_rays(g, sph, ground=2500, surface=2500):
+    """`ground` rays leaving the ground plane at elevations down to grazing, then `surface` rays
+    leaving sphere surfaces in any direction."""
+    rays = []
+    for _ in range(ground):
+        x, z = g.uniform(-5.5, 5.5), g.uniform(-6.5, 2.5)
+        a = g.uniform(0, 2 * np.pi)
+        el = g.choice([g.uniform(0, 0.02), g.uniform(0, 0.3), g.uniform(0, 1.5)])
+        rays.append([x, -0.5, z, np.cos(a) * np.cos(el), np.sin(el), np.sin(a) * np.cos(el)])
+    for _ in range(surface):
+        s = sph[int(g.integers(0, len(sph)))]
+        c = np.array([s.center.x, s.center.y, s.center.z])
+        nrm = g.normal(size=3)
+        nrm /= np.linalg.norm(nrm)
+        rays.append(np.concatenate([c + s.radius * nrm, g.normal(size=3)]))
+    return np.array(rays, np.float32)
 
 
 def test_grazing_and_surface_rays():
@@ -102,19 +136,17 @@ def test_grazing_and_surface_rays():
     grazing the flat field, where the walk crosses the most cells."""
     g = np.random.default_rng(12)
     sph, _ = random_scene(1000, 1)
-    rays = []
-    for _ in range(2500):
-        x, z = g.uniform(-5.5, 5.5), g.uniform(-6.5, 2.5)
-        a = g.uniform(0, 2 * np.pi)
-        el = g.choice([g.uniform(0, 0.02), g.uniform(0, 0.3), g.uniform(0, 1.5)])
-        rays.append([x, -0.5, z, np.cos(a) * np.cos(el), np.sin(el), np.sin(a) * np.cos(el)])
-    for _ in range(2500):
-        s = sph[int(g.integers(0, len(sph)))]
-        c = np.array([s.center.x, s.center.y, s.center.z])
-        nrm = g.normal(size=3)
-        nrm /= np.linalg.norm(nrm)
-        rays.append(np.concatenate([c + s.radius * nrm, g.normal(size=3)]))
-    assert gstats(sph, np.array(rays, np.float32))[3] == 0.0
+    assert gstats(sph, grazing_and_surface_rays(g, sph))[3] == 0.0
+
+
+def far_origin_rays(g, n=300):
+    """Rays towards the scene's middle from 10^4 units away."""
+    far = []
+    for _ in range(n):
+        d = g.normal(size=3)
+        d /= np.linalg.norm(d)
+        far.append(np.concatenate([-d * 1e4 + g.uniform(-1, 1, 3), d]))
+    return np.array(far, np.float32)
 
 
 def test_far_origins_take_the_fallback_scan():
@@ -123,26 +155,35 @@ def test_far_origins_take_the_fallback_scan():
     (origins away from the spheres, GridFarClear) finish with the scan. All exact."""
     g = np.random.default_rng(13)
     sph, _ = random_scene(300, 2)
-    far = []
-    for _ in range(300):
-        d = g.normal(size=3)
-        d /= np.linalg.norm(d)
-        far.append(np.concatenate([-d * 1e4 + g.uniform(-1, 1, 3), d]))
-    res = gstats(sph, np.array(far, np.float32))
+    res = gstats(sph, far_origin_rays(g))
     assert res[3] == 0.0 and res[4] > 0.5, res
     near = gstats(sph, random_rays(g, 500, -8, 8))
     assert near[3] == 0.0 and near[4] < 0.01, near
+
+
+FIELD_BOX = ([-6, -0.6, -7], [6, 3, 4])   # the origins of the random scenes' rays
+
+
+def degenerate_scene():
+    """random_scene(200, 4) with an inf and a NaN centre, a zero radius and two coincident spheres."""
+    sph, _ = random_scene(200, 4)
+    sph[5] = L.Sphere(L.f3(float("inf"), 0, 0), 0.1)
+    sph[6] = L.Sphere(L.f3(0, float("nan"), 0), 0.1)
+    sph[7] = L.Sphere(L.f3(1, 0, 1), 0.0)
+    sph[8] = L.Sphere(L.f3(sph[9].center.x, sph[9].center.y, sph[9].center.z), sph[9].radius)
+    return sph
+
+
+def big_spheres_scene(g):
+    """Three spheres too big for cells and a small one."""
+    return [L.Sphere(L.f3(*g.uniform(-5, 5, 3)), float(r)) for r in (100, 200, 300, 0.1)]
 
 
 def test_non_finite_and_degenerate_scenes():
     """Spheres with inf / NaN fields go to the spheres tested first; zero-radius spheres and
     coincident spheres stay in cells. A scene of only big spheres has no walk at all."""
     g = np.random.default_rng(14)
-    sph, _ = random_scene(200, 4)
-    sph[5] = L.Sphere(L.f3(float("inf"), 0, 0), 0.1)
-    sph[6] = L.Sphere(L.f3(0, float("nan"), 0), 0.1)
-    sph[7] = L.Sphere(L.f3(1, 0, 1), 0.0)
-    sph[8] = L.Sphere(L.f3(sph[9].center.x, sph[9].center.y, sph[9].center.z), sph[9].radius)
-    assert gstats(sph, random_rays(g, 2000, [-6, -0.6, -7], [6, 3, 4]))[3] == 0.0
-    big = [L.Sphere(L.f3(*g.uniform(-5, 5, 3)), float(r)) for r in (100, 200, 300, 0.1)]
+    sph = degenerate_scene()
+    assert gstats(sph, random_rays(g, 2000, *FIELD_BOX))[3] == 0.0
+    big = big_spheres_scene(g)
     assert gstats(big, random_rays(g, 500, -10, 10))[3] == 0.0
