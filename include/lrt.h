@@ -115,7 +115,7 @@ typedef struct lrt_render_desc {
 #define LRT_F_POOL 512       /* v5 kernel: the v0 loop with sample-pool regeneration: a lane
                                 whose path ends takes the wave's next pixel-sample at once;
                                 colours are lerped in frame order per pixel when the pool
-                                is done. No lrt_features.                             */
+                                is done. No lrt_features (lrt_gbuffer_* gives guides). */
 #define LRT_F_BVH 1024       /* closest hits through the 4-wide BVH even where the library
                                 would pick the uniform grid (scenes above 16 spheres) */
 #define LRT_F_GRID 2048      /* closest hits through the uniform grid (lrt_grid.h) even where
@@ -667,6 +667,92 @@ int lrt_tonemap_device(const lrt_tonemap_desc* desc, const float* d_color, lrt_e
  * lrt_tonemap_device's bit for bit. */
 int lrt_tonemap_host(const lrt_tonemap_desc* desc, const float* color, lrt_exposure_state* state,
                      uint32_t* histogram, float* out, uint32_t* bgra);
+
+/* ---- G-buffer: pixel-centre first-hit guides, ids, depth and motion --------------- */
+
+/* The guides of the post-process chain from a pass of their own, as every real-time SVGF pipeline
+ * takes them: one primary ray per pixel through the pixel CENTRE, with no lens and no RNG, against
+ * the scene the library holds. lrt_features (the v0 kernel's side output) are means over jittered
+ * lens samples; these are the values of one exact point per pixel, they come with the sphere's id
+ * and the depth, and any render kernel (LRT_F_POOL, LRT_F_WAVEFRONT) can supply the colour. f32
+ * throughout, no contraction. Whole frames: `height` rows of `width` pixels, row 0 at the bottom.
+ *
+ * Per pixel (x, y), with the camera O, L, H, V (origin, lowerLeftCorner, horizontalVec,
+ * verticalVec; lensRadius, u and r are not read):
+ *  1. s = ((float)x + 0.5f) * (1.0f / (float)width), t likewise with height (the reciprocals are
+ *     taken once, on the host); D = ((L + s H) + t V) - O, in that order: GetRay's expression
+ *     (maths.h:205-215) with a zero lens offset. The ray is Ray(O, D): one normalize.
+ *  2. The closest hit over (kMinT, kMaxT) = (0.001, 1e7), HitWorld's bits: (id, t).
+ *  3. Hit: P = O + dir t, n = normalize(P - c_id), albedo = the material's. Miss: the three guides
+ *     are 0, id = -1, depth = +Inf.
+ *  4. Motion (if requested): steps 3a and 4 of lrt_temporal_* on the exact point. The target is
+ *     d = Xc' - O' for a hit, d = D for a miss; Xc' = P, unless `scene` is given and sphere id's
+ *     eight floats differ in a bit between scene->spheres and scene->prev_spheres: then
+ *     Xc' = c' + (r' / r) (P - c). Into the previous camera as step 4 does: da = d.a',
+ *     fd = -(L' - O').a', q = (-fd / da) d - (L' - O'), fx = (q.H') (1 / H'.H') w - 1/2,
+ *     fy = (q.V') (1 / V'.V') h - 1/2; projectable iff da < 0 and |fx|, |fy| < 1e6 (a NaN fails).
+ *     A hit sphere with r' <= 0 (or r <= 0) did not exist in the previous frame: not projectable.
+ *     Under bit-identical cameras (origin, a, lowerLeftCorner, horizontalVec, verticalVec) a miss
+ *     and a hit on a sphere that did not move take their own centre, fx = x, fy = y, with no
+ *     arithmetic: the temporal step's own rule.
+ * Outputs (each optional): normal, world_pos, albedo = guide_scale * (n, P, albedo) in rgb, alpha
+ * written 0; id; depth = t; motion = (fx - x, fy - y, (float)id, 1) if projectable, else
+ * (0, 0, (float)id, 0): the layout of lrt_temporal_accumulate_moving_*'s motion.
+ *
+ * guide_scale exists because lrt_temporal_desc.cur_scale = k multiplies colour and guides alike: a
+ * caller who renders fresh seeds (frame0 > 0) into zeroed buffers needs
+ * k = (frame0 + frames) / frames for the colour, passes guide_scale = 1 / k here, and the temporal
+ * step then sees these guides at scale 1, within rounding. id and depth are never scaled.
+ *
+ * id and depth are pinned bit for bit to the library's closest hit (lrt_accel_eval, lrt_diag.h);
+ * the guides and the motion are tolerance-checked against the NumPy restatement
+ * (tests/gbuffer_ref.py). Limits: whole frames, the first device, spheres only, first hits only
+ * (no lens, no jitter: an edge pixel is one surface or the other, never a mixture). */
+typedef struct lrt_gbuffer_desc {
+    int32_t width, height;          /* a whole frame */
+    int32_t flags, reserved;        /* 0 */
+    lrt_camera camera, prev_camera; /* prev_camera is read only when motion is requested */
+    float guide_scale;              /* finite, > 0; default 1 */
+    int32_t reserved2;              /* 0 */
+} lrt_gbuffer_desc;
+
+typedef struct lrt_gbuffer {        /* every member optional, at least one non-NULL */
+    float* normal;     /* RGBA quads: rgb = guide_scale * n, alpha written 0 */
+    float* world_pos;  /* RGBA quads: rgb = guide_scale * P, alpha written 0 */
+    float* albedo;     /* RGBA quads: rgb = guide_scale * material albedo, alpha written 0 */
+    float* motion;     /* RGBA quads, all four written (layout of lrt_temporal's motion) */
+    int32_t* id;       /* width*height: sphere index, -1 on a miss */
+    float* depth;      /* width*height: t along the unit ray; +Inf on a miss */
+} lrt_gbuffer;
+
+/* The defaults for a width x height frame and a camera pair: guide_scale 1. prev_camera == NULL:
+ * the camera. */
+int lrt_gbuffer_default(int width, int height, const lrt_camera* camera,
+                        const lrt_camera* prev_camera, lrt_gbuffer_desc* out);
+
+/* The pass into device buffers. `scene` may be NULL (nothing moved); if given, scene->spheres must
+ * be the scene the library holds (what lrt_get_scene returns, bit for bit) and both arrays are read
+ * from host memory before the call returns: up to 64 spheres travel in the kernel's own arguments,
+ * more are uploaded on `stream` into that stream's scratch, as in
+ * lrt_temporal_accumulate_moving_device. Only the planes given are written, and nothing else is
+ * paid for. Scenes of up to 16 spheres are scanned, larger ones go through the uniform grid (built
+ * on first use, as a render would).
+ *
+ * LRT_E_INVALID, before any device use: NULL desc or d_out, or all six planes NULL; sizes < 1 or
+ * width * height > INT_MAX / 4; flags, reserved or reserved2 != 0; guide_scale not finite or <= 0;
+ * any two planes overlapping (address ranges); with motion, a prev_camera that lrt_temporal_*
+ * rejects; with `scene`, a NULL array, count outside 1..LRT_MAX_SPHERES, reserved != 0, a
+ * non-finite float, a count other than the current scene's, or spheres that are not the current
+ * scene's bit for bit (an uninitialised library holds no scene: any `scene` is refused). Then
+ * LRT_E_STATE without lrt_initialize(). Asynchronous on `stream` and ordered only against it; it
+ * sees the scene as an lrt_render_device call made at the same moment would. Acts on the first
+ * device. */
+int lrt_gbuffer_device(const lrt_gbuffer_desc* desc, const lrt_scene_motion* scene,
+                       const lrt_gbuffer* d_out, void* stream);
+
+/* Same into HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_gbuffer_device's bit for bit. */
+int lrt_gbuffer_host(const lrt_gbuffer_desc* desc, const lrt_scene_motion* scene, const lrt_gbuffer* out);
 
 #ifdef __cplusplus
 }

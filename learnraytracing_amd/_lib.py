@@ -159,6 +159,23 @@ class ExposureState(ctypes.Structure):        # lrt_exposure_state
                 ("counted", ctypes.c_float), ("frames", ctypes.c_float)]
 
 
+class GbufferDesc(ctypes.Structure):         # lrt_gbuffer_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("camera", Camera), ("prev_camera", Camera),
+                ("guide_scale", ctypes.c_float), ("reserved2", ctypes.c_int32)]
+
+
+class Gbuffer(ctypes.Structure):              # lrt_gbuffer
+    _fields_ = [("normal", ctypes.c_void_p), ("world_pos", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
+                ("motion", ctypes.c_void_p), ("id", ctypes.c_void_p), ("depth", ctypes.c_void_p)]
+
+
+GBUFFER_GUIDE_NAMES = ("normal", "world_pos", "albedo")   # always returned
+GBUFFER_EXTRA_NAMES = ("id", "depth", "motion")           # on request
+GBUFFER_NAMES = GBUFFER_GUIDE_NAMES + GBUFFER_EXTRA_NAMES
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -217,6 +234,9 @@ SIGNATURES = {
     "lrt_tonemap_default": (_i, [_i, _i, _c.POINTER(TonemapDesc)]),
     "lrt_tonemap_device": (_i, [_c.POINTER(TonemapDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     "lrt_tonemap_host": (_i, [_c.POINTER(TonemapDesc), _vp, _vp, _vp, _vp, _vp]),
+    "lrt_gbuffer_default": (_i, [_i, _i, _c.POINTER(Camera), _c.POINTER(Camera), _c.POINTER(GbufferDesc)]),
+    "lrt_gbuffer_device": (_i, [_c.POINTER(GbufferDesc), _c.POINTER(SceneMotion), _c.POINTER(Gbuffer), _vp]),
+    "lrt_gbuffer_host": (_i, [_c.POINTER(GbufferDesc), _c.POINTER(SceneMotion), _c.POINTER(Gbuffer)]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

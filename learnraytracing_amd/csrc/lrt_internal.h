@@ -13,12 +13,14 @@
 //   lrt_temporal.hip  temporal reprojection and accumulation (lrt_temporal_*): kernel and entry points
 //   lrt_svgf.hip      the variance-guided filter over the temporal state (lrt_svgf_*): kernels and entry points
 //   lrt_tonemap.hip   auto-exposure metering and tone mapping (lrt_tonemap_*): kernels and entry points
+//   lrt_gbuffer.hip   the pixel-centre G-buffer pass (lrt_gbuffer_*): kernel and entry points
 //   lrt_atrous.h      the lattice tile of the two a-trous kernels (denoise, svgf): geometry, anchor, staging, taps
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
-// The host plumbing that the four post-process units (denoise, temporal, svgf, tonemap) share is
+// The host plumbing that the post-process units (denoise, temporal, svgf, tonemap, gbuffer) share is
 // below: the size and aliasing checks, the staging allocation of a *_host call, the stream scratch
-// of a *_device call, the ready check.
+// of a *_device call, the ready check, and the two-scene sphere arrays (lrt_scene_motion) of the
+// temporal and the G-buffer kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -466,6 +468,49 @@ inline int scratch_or_fail(hipStream_t s, size_t bytes, const char* what, void**
     if (e == hipSuccess) return LRT_OK;
     return e == hipErrorOutOfMemory ? fail(LRT_E_NOMEM, what) : hip_fail(e, what);
 }
+
+// A previous camera that step 4 of lrt_temporal_* can project into: H'.H', V'.V' and the focus
+// distance along its axis, fd = -(L' - O').a', are finite and > 0.
+inline float prev_camera_fd(const lrt_camera& c) {
+    return -((c.lowerLeftCorner.x - c.origin.x) * c.a.x + (c.lowerLeftCorner.y - c.origin.y) * c.a.y +
+             (c.lowerLeftCorner.z - c.origin.z) * c.a.z);
+}
+inline int validate_prev_camera(const lrt_camera& pc) {
+    const lrt_float3 &H = pc.horizontalVec, &V = pc.verticalVec;
+    for (float v : {H.x * H.x + H.y * H.y + H.z * H.z, V.x * V.x + V.y * V.y + V.z * V.z, prev_camera_fd(pc)})
+        if (!std::isfinite(v) || !(v > 0.0f))
+            return fail(LRT_E_INVALID, "prev_camera: H.H, V.V and the focus distance must be finite and > 0");
+    return LRT_OK;
+}
+// The arrays, count, reserved word and floats of an lrt_scene_motion.
+inline int validate_scene_motion(const lrt_scene_motion* sm) {
+    if (!sm || !sm->spheres || !sm->prev_spheres)
+        return fail(LRT_E_INVALID, "scene motion needs spheres and prev_spheres");
+    if (sm->count < 1 || sm->count > LRT_MAX_SPHERES) return fail(LRT_E_INVALID, "sphere count out of range");
+    if (sm->reserved != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
+    for (const lrt_sphere* arr : {sm->spheres, sm->prev_spheres})
+        for (int i = 0; i < sm->count; ++i)
+            for (float v : {arr[i].center.x, arr[i].center.y, arr[i].center.z, arr[i].radius})
+                if (!std::isfinite(v)) return fail(LRT_E_INVALID, "spheres must be finite");
+    return LRT_OK;
+}
+
+// ---- lrt_temporal.hip: the two sphere arrays of an lrt_scene_motion as a kernel reads them, 2 x
+// count float4: sph[i] = (c_i, r_i), or radius -1 where sphere i is no candidate (r_i <= 0 or
+// r'_i <= 0); psph[i] = (c'_i, r'_i / r_i), or ratio -1 where the sphere's eight floats are the same
+// bits in both scenes. A scene of up to kInlineSpheres spheres travels in the kernel's arguments
+// (the packed arrays back to back, psph at v + count): no upload, hence no copy command between
+// two calls' kernels, which at 9 spheres cost more than the temporal match itself.
+constexpr int kInlineSpheres = 64;
+struct InlineSpheres {
+    float4 v[2 * kInlineSpheres];
+};
+void pack_motion(const lrt_scene_motion* sm, float4* dst);
+// The packed arrays into stream s's scratch, in stream order: the host arrays are read here, into
+// a page-locked slot (Context::motion_slots), and the copy out of it is asynchronous. *d_sph: the
+// device copy (psph at *d_sph + count). The caller marks the scratch used after its launch
+// (stream_scratch_used).
+int upload_motion(const lrt_scene_motion* sm, hipStream_t s, const char* what, const float4** d_sph);
 
 // ---- lrt_v0_d8.hip / lrt_v0_d64.hip: v0 launches for max_depth <= 8 / <= 64. colours: the
 // pipelined host path's colours-only render (one frame lane, sample planes)

@@ -49,13 +49,7 @@ struct MotionArgs {
     float4* motion;   // or null
     int count;
 };
-// A scene of up to kInlineSpheres spheres travels in the kernel's arguments instead (the packed
-// arrays back to back, psph at v + count): no upload, hence no copy command between two steps'
-// kernels, which at 9 spheres cost more than the match itself.
-constexpr int kInlineSpheres = 64;
-struct InlineSpheres {
-    float4 v[2 * kInlineSpheres];
-};
+// (up to kInlineSpheres spheres travel in the kernel's arguments instead: InlineSpheres, lrt_internal.h)
 constexpr int kMoveOff = 0, kMoveScratch = 1, kMoveInline = 2;   // temporal_pixel's kMove
 
 LRT_DEV float3 rgb(const float4 v) { return make_float3(v.x, v.y, v.z); }
@@ -248,8 +242,6 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_moving_inline_kerne
 static float3 f3(const lrt_float3& v) { return make_float3(v.x, v.y, v.z); }
 static float hdot(const float3 a, const float3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 static float3 hsub(const float3 a, const float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
-// the previous camera's focus distance along its axis: fd = -(L' - O').a'
-static float prev_fd(const lrt_camera& c) { return -hdot(hsub(f3(c.lowerLeftCorner), f3(c.origin)), f3(c.a)); }
 
 static int validate_temporal(const lrt_temporal_desc* d, const float* color, const lrt_features* cur,
                              const lrt_temporal_state* prev, const lrt_temporal_state* next, const float* std) {
@@ -269,11 +261,7 @@ static int validate_temporal(const lrt_temporal_desc* d, const float* color, con
         return fail(LRT_E_INVALID, "cur_scale, pos_tol and short_std must be > 0");
     if (!(d->alpha_min > 0.0f && d->alpha_min <= 1.0f)) return fail(LRT_E_INVALID, "alpha_min must be in (0, 1]");
     if (!(d->normal_min >= -1.0f && d->normal_min <= 1.0f)) return fail(LRT_E_INVALID, "normal_min must be in [-1, 1]");
-    const lrt_camera& pc = d->prev_camera;
-    for (float v : {hdot(f3(pc.horizontalVec), f3(pc.horizontalVec)), hdot(f3(pc.verticalVec), f3(pc.verticalVec)),
-                    prev_fd(pc)})
-        if (!std::isfinite(v) || !(v > 0.0f))
-            return fail(LRT_E_INVALID, "prev_camera: H.H, V.V and the focus distance must be finite and > 0");
+    if (int rc = validate_prev_camera(d->prev_camera)) return rc;
     // no output may overlap an input, a prev buffer or another output
     const size_t bytes = (size_t)d->width * d->height * 4 * sizeof(float);
     const float* const outs[6] = {next->color, next->moment2, next->normal, next->world_pos, next->albedo, std};
@@ -296,14 +284,7 @@ static int validate_temporal(const lrt_temporal_desc* d, const float* color, con
 static int validate_motion(const lrt_temporal_desc* d, const lrt_scene_motion* sm, const float* color,
                            const lrt_features* cur, const lrt_temporal_state* prev, const lrt_temporal_state* next,
                            const float* std, const float* motion) {
-    if (!sm || !sm->spheres || !sm->prev_spheres)
-        return fail(LRT_E_INVALID, "scene motion needs spheres and prev_spheres");
-    if (sm->count < 1 || sm->count > LRT_MAX_SPHERES) return fail(LRT_E_INVALID, "sphere count out of range");
-    if (sm->reserved != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
-    for (const lrt_sphere* arr : {sm->spheres, sm->prev_spheres})
-        for (int i = 0; i < sm->count; ++i)
-            for (float v : {arr[i].center.x, arr[i].center.y, arr[i].center.z, arr[i].radius})
-                if (!std::isfinite(v)) return fail(LRT_E_INVALID, "spheres must be finite");
+    if (int rc = validate_scene_motion(sm)) return rc;
     const size_t bytes = (size_t)d->width * d->height * 4 * sizeof(float);
     const float* const others[15] = {color, cur->normal, cur->world_pos, cur->albedo,
                                      prev ? prev->color : nullptr, prev ? prev->moment2 : nullptr,
@@ -316,8 +297,8 @@ static int validate_motion(const lrt_temporal_desc* d, const lrt_scene_motion* s
     return LRT_OK;
 }
 
-// The two sphere arrays as the kernel reads them (MotionArgs), 2 x count float4 into dst.
-static void pack_motion(const lrt_scene_motion* sm, float4* dst) {
+// The two sphere arrays as the kernels read them (MotionArgs; lrt_internal.h), 2 x count float4 into dst.
+void pack_motion(const lrt_scene_motion* sm, float4* dst) {
     const int n = sm->count;
     for (int i = 0; i < n; ++i) {
         const lrt_sphere &c = sm->spheres[i], &p = sm->prev_spheres[i];
@@ -359,19 +340,17 @@ static int motion_slot(Context& c, Context::MotionSlot** out) {
 }
 
 // The packed spheres into stream s's scratch, in stream order: the host arrays are read here, into
-// a page-locked slot, and the copy out of it is asynchronous. *ma gets the device pointers.
-static int upload_motion(const lrt_scene_motion* sm, hipStream_t s, MotionArgs* ma) {
+// a page-locked slot, and the copy out of it is asynchronous. *d_sph gets the device copy.
+int upload_motion(const lrt_scene_motion* sm, hipStream_t s, const char* what, const float4** d_sph) {
     Context::MotionSlot* slot = nullptr;
     if (int rc = motion_slot(ctx(), &slot)) return rc;
     const size_t bytes = 2 * (size_t)sm->count * sizeof(float4);
     void* d = nullptr;
-    if (int rc = scratch_or_fail(s, bytes, "temporal scratch", &d)) return rc;
+    if (int rc = scratch_or_fail(s, bytes, what, &d)) return rc;
     pack_motion(sm, static_cast<float4*>(slot->h));
     LRT_HIP(hipMemcpyAsync(d, slot->h, bytes, hipMemcpyHostToDevice, s));
     LRT_HIP(hipEventRecord(slot->ev, s));
-    ma->sph = static_cast<const float4*>(d);
-    ma->psph = ma->sph + sm->count;
-    ma->count = sm->count;
+    *d_sph = static_cast<const float4*>(d);
     return LRT_OK;
 }
 
@@ -385,8 +364,11 @@ static int temporal_device(const lrt_temporal_desc* d, const float* color, const
     ma.motion = reinterpret_cast<float4*>(motion);
     const bool inl = sm && prev && sm->count <= kInlineSpheres;   // the spheres in the kernel's arguments
     const bool upl = sm && prev && !inl;                         // ... or uploaded to the stream's scratch
-    if (upl)
-        if (int rc = upload_motion(sm, s, &ma)) return rc;
+    if (upl) {
+        if (int rc = upload_motion(sm, s, "temporal scratch", &ma.sph)) return rc;
+        ma.psph = ma.sph + sm->count;
+        ma.count = sm->count;
+    }
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
     auto q = [](const float* p) { return reinterpret_cast<const float4*>(p); };
@@ -414,7 +396,7 @@ static int temporal_device(const lrt_temporal_desc* d, const float* color, const
     a.pLO = hsub(f3(p.lowerLeftCorner), a.pO);
     a.pH = f3(p.horizontalVec);
     a.pV = f3(p.verticalVec);
-    a.fd = prev_fd(p);
+    a.fd = prev_camera_fd(p);
     a.rhh = 1.0f / hdot(a.pH, a.pH);
     a.rvv = 1.0f / hdot(a.pV, a.pV);
     a.k = d->cur_scale;

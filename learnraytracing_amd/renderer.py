@@ -870,6 +870,104 @@ class ToneMapper:
         return dict(zip(("log2_exposure", "log2_luminance", "counted", "frames"), v))
 
 
+# ---- G-buffer: pixel-centre first-hit guides, ids, depth and motion -------------------------
+def gbuffer_desc(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera] = None,
+                 guide_scale: float = 1.0) -> L.GbufferDesc:
+    """lrt_gbuffer_default for a width x height frame seen from `camera`, the previous frame from
+    `prev_camera` (None: the same camera), with guide_scale set."""
+    if not isinstance(camera, L.Camera) or not (prev_camera is None or isinstance(prev_camera, L.Camera)):
+        raise L.LrtError(L.LRT_E_INVALID, "camera and prev_camera must be Camera structs")
+    d = L.GbufferDesc()
+    L.check(L.lib().lrt_gbuffer_default(int(width), int(height), ctypes.byref(camera),
+                                        ctypes.byref(prev_camera) if prev_camera is not None else None,
+                                        ctypes.byref(d)))
+    d.guide_scale = float(guide_scale)
+    return d
+
+
+def _gbuffer_call(entry, width, height, out, want, make, ptr, check, spheres, prev_spheres, extra):
+    """The marshalling the host and tensor front ends share. out: the caller's planes {name: buffer}
+    (only those are written), or None for new ones: the three guides and whatever `want` names.
+    make(name) is a new plane, ptr(buf) its address, check(buf, name) validates one."""
+    if out is None:
+        out = {name: make(name) for name in L.GBUFFER_GUIDE_NAMES + tuple(n for n in L.GBUFFER_EXTRA_NAMES if want[n])}
+    g = L.Gbuffer()
+    for name, buf in out.items():
+        if name not in L.GBUFFER_NAMES:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown G-buffer plane {name!r}")
+        check(buf, name)
+        setattr(g, name, ptr(buf))
+    sm = None
+    if prev_spheres is not None:
+        sm = _scene_motion(spheres if spheres is not None else get_scene()[0], prev_spheres)
+    elif spheres is not None:
+        raise L.LrtError(L.LRT_E_INVALID, "spheres needs prev_spheres")
+    L.check(entry(ctypes.byref(sm) if sm is not None else None, ctypes.byref(g), *extra))
+    return out
+
+
+def gbuffer_host(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera] = None,
+                 id: bool = False, depth: bool = False, motion: bool = False, spheres=None, prev_spheres=None,
+                 guide_scale: float = 1.0, out: Optional[dict] = None) -> dict:
+    """The G-buffer of the current scene seen from `camera` through the pixel centres
+    (lrt_gbuffer_host): {"normal", "world_pos", "albedo"} as float32 [height, width, 4] (what
+    TemporalAccumulator.step, denoise_* and svgf_* take as features or guides), each times
+    guide_scale, plus "id" (int32 [height, width], -1 on a miss), "depth" (float32 [height, width],
+    +Inf on a miss) and "motion" (float32 [height, width, 4]: previous minus current position in
+    pixels, the sphere, 1 if projectable) when asked for. prev_camera: the previous frame's camera
+    (motion only). prev_spheres: the previous frame's scene where spheres moved (Sphere structs or
+    floats [count, 4]); spheres: the current one (default: what the library holds; it must be that).
+    out: the caller's planes instead, any subset of the six names; only those are written."""
+    w, h = int(width), int(height)
+    d = gbuffer_desc(w, h, camera, prev_camera, guide_scale)
+
+    def make(name):
+        if name == "id":
+            return np.zeros((h, w), np.int32)
+        return np.zeros((h, w) if name == "depth" else (h, w, 4), np.float32)
+
+    def check(buf, name):
+        n = w * h * (1 if name in ("id", "depth") else 4)
+        dt = np.int32 if name == "id" else np.float32
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
+            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
+
+    return _gbuffer_call(lambda *a: L.lib().lrt_gbuffer_host(ctypes.byref(d), *a), w, h, out,
+                         dict(id=id, depth=depth, motion=motion), make, lambda b: b.ctypes.data, check,
+                         spheres, prev_spheres, ())
+
+
+def gbuffer_tensor(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera] = None,
+                   id: bool = False, depth: bool = False, motion: bool = False, spheres=None, prev_spheres=None,
+                   guide_scale: float = 1.0, out: Optional[dict] = None, stream=None, device="cuda:0") -> dict:
+    """gbuffer_host into cuda tensors (lrt_gbuffer_device): asynchronous on `stream` (a
+    torch.cuda.Stream, default: current) and ordered only against it; the sphere arrays are read
+    before it returns. "id" is an int32 tensor, the others float32."""
+    import torch
+
+    w, h = int(width), int(height)
+    d = gbuffer_desc(w, h, camera, prev_camera, guide_scale)
+    dev = next(iter(out.values())).device if out else torch.device(device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+
+    def make(name):
+        with torch.cuda.stream(s):
+            if name == "id":
+                return torch.zeros((h, w), dtype=torch.int32, device=dev)
+            return torch.zeros((h, w) if name == "depth" else (h, w, 4), device=dev)
+
+    def check(t, name):
+        n = w * h * (1 if name in ("id", "depth") else 4)
+        dt = torch.int32 if name == "id" else torch.float32
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()
+                and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a contiguous cuda {dt} tensor of >= {n} elements")
+
+    return _gbuffer_call(lambda *a: L.lib().lrt_gbuffer_device(ctypes.byref(d), *a), w, h, out,
+                         dict(id=id, depth=depth, motion=motion), make, lambda t: t.data_ptr(), check,
+                         spheres, prev_spheres, (ctypes.c_void_p(s.cuda_stream),))
+
+
 def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
     """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
     import torch
