@@ -393,7 +393,8 @@ int lrt_denoise_host(const lrt_denoise_desc* desc, const float* color, const lrt
  * kernels (a static camera re-rendering frame0 = 0 would accumulate identical frames).
  *
  * Limits: whole frames only. Static scene: the camera moves, the spheres do not (for spheres that
- * move between two frames there is lrt_temporal_accumulate_moving_* below). First-hit
+ * move between two frames there is lrt_temporal_accumulate_moving_* below, and
+ * lrt_temporal_accumulate_gbuffer_* further down takes ids and motion vectors instead). First-hit
  * reprojection only: reflections and refractions lag. Like the denoiser it is not bit-pinned (the
  * reference has no such stage) but tolerance-checked against its NumPy restatement
  * (tests/temporal_ref.py); it is deterministic run to run. */
@@ -753,6 +754,77 @@ int lrt_gbuffer_device(const lrt_gbuffer_desc* desc, const lrt_scene_motion* sce
 /* Same into HOST buffers: staged through device memory, blocking; every output equals
  * lrt_gbuffer_device's bit for bit. */
 int lrt_gbuffer_host(const lrt_gbuffer_desc* desc, const lrt_scene_motion* scene, const lrt_gbuffer* out);
+
+/* ---- temporal accumulation driven by the G-buffer's ids and motion vectors -------- */
+
+/* lrt_temporal_accumulate_* as every real-time SVGF pipeline has it: the step takes the motion
+ * vectors and the ids that lrt_gbuffer_* wrote, and needs no cameras, no scenes and no loop over
+ * the spheres (its cost does not depend on their count). The state it keeps is color and moment2
+ * only: the previous frame's normal and id are read from the previous G-buffer's own planes.
+ *
+ * Per pixel (x, y), with C = cur_scale color.rgb, N = normal.rgb as read, i = id and
+ * (mx, my, ., mw) = motion of the current G-buffer, N', i' of the previous one:
+ *  1. fx = x + mx, fy = y + my; ok = mw != 0 and |fx|, |fy| < 1e6 (a NaN fails). A zero motion
+ *     gives fx = x with no rounding: what lrt_gbuffer_* guarantees under a static camera carries
+ *     through, and a static accumulation never bleeds its neighbours in.
+ *  2. The four bilinear taps Q of step 5 of lrt_temporal_*. A tap counts iff it lies inside the
+ *     image and i'(Q) = i; for a hit (i >= 0) it also needs N'(Q).N >= normal_min. A miss matches
+ *     a miss (-1 = -1). No id is ever used as an index.
+ *  3. Steps 6 and 7 of lrt_temporal_*, unchanged.
+ * Outputs: next->color rgb (alpha untouched), next->moment2 (rgb and n), color_std rgb (alpha
+ * untouched) if requested. Nothing else is written.
+ *
+ * cur_scale multiplies the COLOUR only: the planes must be those of an lrt_gbuffer_* call with
+ * guide_scale 1 (unit normals).
+ *
+ * Limits: first-hit motion only (shadows, reflections and refractions lag). The test is id plus
+ * normal: a point that was behind its own sphere's silhouette in the previous frame is rejected
+ * by the normal test only. Spheres only, whole frames only, the first device. Guides must be at
+ * scale 1. Tolerance-checked against its NumPy restatement (tests/temporal_gbuffer_ref.py);
+ * deterministic run to run. */
+typedef struct lrt_temporal_gbuffer_desc {
+    int32_t width, height;      /* a whole frame */
+    int32_t flags;              /* 0 */
+    int32_t min_history;        /* >= 1 */
+    float cur_scale;            /* finite, > 0: multiplies the COLOUR only */
+    float alpha_min;            /* in (0, 1] */
+    float normal_min;           /* in [-1, 1] */
+    float short_std;            /* finite, > 0 */
+    int32_t reserved, reserved2;/* 0 */
+} lrt_temporal_gbuffer_desc;
+
+/* The defaults for a width x height frame, lrt_temporal_default's: alpha_min 0.05, normal_min 0.9,
+ * min_history 4, short_std 1e3, cur_scale 1. */
+int lrt_temporal_gbuffer_default(int width, int height, lrt_temporal_gbuffer_desc* out);
+
+/* One step on device buffers. d_color: the current frame's colour. d_cur: the current G-buffer;
+ * normal, motion and id are required, the other members are ignored. d_prev_g: the previous
+ * frame's G-buffer; normal and id are required. d_prev / d_next: the previous state and the one
+ * written; of either only color and moment2 are required, read or written, and the other three
+ * members are never touched. d_prev and d_prev_g are both NULL (no history: every pixel is reset)
+ * or both given. d_color_std may be NULL.
+ *
+ * LRT_E_INVALID, before any device use: NULL required pointers; exactly one of d_prev and
+ * d_prev_g; sizes < 1 or width * height > INT_MAX / 4; flags, reserved or reserved2 != 0;
+ * min_history < 1; non-finite parameters; cur_scale or short_std <= 0; alpha_min outside (0, 1];
+ * normal_min outside [-1, 1]; d_next->color, d_next->moment2 or d_color_std overlapping an input,
+ * a previous buffer or each other (by address range: the id planes are width * height * 4 bytes,
+ * the others 16 bytes per pixel); d_cur->normal or d_cur->id overlapping d_prev_g's (a G-buffer
+ * overwritten in place is no history: ping-pong two). Then LRT_E_STATE without lrt_initialize().
+ * Asynchronous on `stream` and ordered only against it, with no host round trip. Acts on the
+ * first device. */
+int lrt_temporal_accumulate_gbuffer_device(const lrt_temporal_gbuffer_desc* desc, const float* d_color,
+                                           const lrt_gbuffer* d_cur, const lrt_gbuffer* d_prev_g,
+                                           const lrt_temporal_state* d_prev, const lrt_temporal_state* d_next,
+                                           float* d_color_std, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_temporal_accumulate_gbuffer_device's bit for bit (the alphas of next->color and color_std
+ * are the host buffers' own). */
+int lrt_temporal_accumulate_gbuffer_host(const lrt_temporal_gbuffer_desc* desc, const float* color,
+                                         const lrt_gbuffer* cur, const lrt_gbuffer* prev_g,
+                                         const lrt_temporal_state* prev, const lrt_temporal_state* next,
+                                         float* color_std);
 
 #ifdef __cplusplus
 }

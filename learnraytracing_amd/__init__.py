@@ -14,6 +14,7 @@ from .renderer import (DrawTest, InitializeDevices, InitializeTest, Job, Shutdow
                        svgf_desc, svgf_filter_host, svgf_filter_tensor,
                        temporal_accumulate_host, temporal_accumulate_moving_host, temporal_accumulate_moving_tensor,
                        temporal_accumulate_tensor, temporal_desc,
+                       temporal_accumulate_gbuffer_host, temporal_accumulate_gbuffer_tensor, temporal_gbuffer_desc,
                        tonemap_desc, tonemap_host, tonemap_tensor,
                        gbuffer_desc, gbuffer_host, gbuffer_tensor)
 from .scene import default_scene, random_scene  # noqa: F401

@@ -176,6 +176,20 @@ GBUFFER_EXTRA_NAMES = ("id", "depth", "motion")           # on request
 GBUFFER_NAMES = GBUFFER_GUIDE_NAMES + GBUFFER_EXTRA_NAMES
 
 
+class TemporalGbufferDesc(ctypes.Structure):  # lrt_temporal_gbuffer_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("min_history", ctypes.c_int32),
+                ("cur_scale", ctypes.c_float), ("alpha_min", ctypes.c_float), ("normal_min", ctypes.c_float),
+                ("short_std", ctypes.c_float), ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
+
+
+TEMPORAL_GBUFFER_PARAMS = ("cur_scale", "alpha_min", "normal_min", "short_std", "min_history")
+TEMPORAL_GBUFFER_CUR_NAMES = ("normal", "motion", "id")    # what lrt_temporal_accumulate_gbuffer_* reads of d_cur
+TEMPORAL_GBUFFER_PREV_NAMES = ("normal", "id")             # ... of d_prev_g
+TEMPORAL_GBUFFER_STATE_NAMES = ("color", "moment2")        # ... and reads or writes of a state
+TEMPORAL_GBUFFER_PLANES = ("normal", "world_pos", "albedo", "motion", "id")   # TemporalAccumulator.gbuffer_planes()
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -237,6 +251,13 @@ SIGNATURES = {
     "lrt_gbuffer_default": (_i, [_i, _i, _c.POINTER(Camera), _c.POINTER(Camera), _c.POINTER(GbufferDesc)]),
     "lrt_gbuffer_device": (_i, [_c.POINTER(GbufferDesc), _c.POINTER(SceneMotion), _c.POINTER(Gbuffer), _vp]),
     "lrt_gbuffer_host": (_i, [_c.POINTER(GbufferDesc), _c.POINTER(SceneMotion), _c.POINTER(Gbuffer)]),
+    "lrt_temporal_gbuffer_default": (_i, [_i, _i, _c.POINTER(TemporalGbufferDesc)]),
+    "lrt_temporal_accumulate_gbuffer_device": (_i, [_c.POINTER(TemporalGbufferDesc), _vp, _c.POINTER(Gbuffer),
+                                                    _c.POINTER(Gbuffer), _c.POINTER(TemporalState),
+                                                    _c.POINTER(TemporalState), _vp, _vp]),
+    "lrt_temporal_accumulate_gbuffer_host": (_i, [_c.POINTER(TemporalGbufferDesc), _vp, _c.POINTER(Gbuffer),
+                                                  _c.POINTER(Gbuffer), _c.POINTER(TemporalState),
+                                                  _c.POINTER(TemporalState), _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

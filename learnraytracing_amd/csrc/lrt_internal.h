@@ -11,6 +11,8 @@
 //   lrt_frame.hip     frame assembly and present kernels (the quantiser itself: lrt_srgb.h)
 //   lrt_denoise.hip   the feature-guided a-trous denoiser (lrt_denoise_*): kernel and entry points
 //   lrt_temporal.hip  temporal reprojection and accumulation (lrt_temporal_*): kernel and entry points
+//   lrt_temporal_gbuffer.hip  the step driven by the G-buffer's ids and motion (lrt_temporal_accumulate_gbuffer_*)
+//   lrt_temporal_blend.h      steps 6 and 7 of the temporal rule, shared by the two units above
 //   lrt_svgf.hip      the variance-guided filter over the temporal state (lrt_svgf_*): kernels and entry points
 //   lrt_tonemap.hip   auto-exposure metering and tone mapping (lrt_tonemap_*): kernels and entry points
 //   lrt_gbuffer.hip   the pixel-centre G-buffer pass (lrt_gbuffer_*): kernel and entry points

@@ -15,6 +15,8 @@
 
 #pragma clang fp contract(fast)
 
+#include "lrt_temporal_blend.h"   // step 7, under this unit's contraction
+
 namespace lrt {
 
 struct TemporalArgs {
@@ -193,7 +195,7 @@ __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const Moti
             sc = mad3(bw, rgb(qc[i]), sc);
             sm = mad3(bw, rgb(qm[i]), sm);
         }
-        if (sw > 1e-3f) {
+        if (sw > 1e-3f) {   // (temporal_blend's lines, kept here: through the call these kernels' moves reorder)
             const float r = 1.0f / sw;
             n = sn * r + 1.0f;
             const float al = fmaxf(1.0f / n, a.alpha_min), be = (1.0f - al) * r;
@@ -210,10 +212,7 @@ __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const Moti
     a.ox[ip] = make_float4(X.x, X.y, X.z, 0.0f);
     if (a.oa) a.oa[ip] = make_float4(k * a4.x, k * a4.y, k * a4.z, 0.0f);
     if (a.ostd) {
-        float3 sd = make_float3(a.short_std, a.short_std, a.short_std);
-        if (!(n < a.min_history))
-            sd = make_float3(sqrtf(fmaxf(m2.x - col.x * col.x, 0.0f)), sqrtf(fmaxf(m2.y - col.y * col.y, 0.0f)),
-                             sqrtf(fmaxf(m2.z - col.z * col.z, 0.0f)));
+        const float3 sd = temporal_std(col, m2, n, a.short_std, a.min_history);
         float* const os = reinterpret_cast<float*>(a.ostd + ip);
         os[0] = sd.x;
         os[1] = sd.y;

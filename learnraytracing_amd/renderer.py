@@ -588,10 +588,127 @@ def temporal_accumulate_moving_tensor(color, cur: dict, prev: Optional[dict], ca
                           (mp, ctypes.c_void_p(s.cuda_stream)))
 
 
+def temporal_gbuffer_desc(width: int, height: int, **params) -> L.TemporalGbufferDesc:
+    """lrt_temporal_gbuffer_default for a width x height frame, with any of cur_scale, alpha_min,
+    normal_min, short_std, min_history overridden."""
+    d = L.TemporalGbufferDesc()
+    L.check(L.lib().lrt_temporal_gbuffer_default(int(width), int(height), ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.TEMPORAL_GBUFFER_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown temporal parameter {name!r}")
+        setattr(d, name, int(v) if name == "min_history" else float(v))
+    return d
+
+
+def _temporal_gbuffer_call(entry, color, cur, prev_g, prev, out, check, ptr, make, extra):
+    """The argument marshalling the host and tensor front ends share: check(buf, what, name)
+    validates a plane called `name` (int32 of width x height for "id", else float32 quads), ptr(buf)
+    is its address, make() a zeroed frame. Returns the new state."""
+    check(color, "color", "color")
+
+    def planes(d, need, what):
+        if not isinstance(d, dict) or any(n not in d for n in need):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must hold " + " and ".join(need))
+        g = L.Gbuffer()
+        for name, buf in d.items():
+            if name not in L.GBUFFER_NAMES:
+                raise L.LrtError(L.LRT_E_INVALID, f"unknown G-buffer plane {name!r}")
+            if name in need:                  # a whole G-buffer may be passed as it is: the rest is not read
+                check(buf, f"{what} {name}", name)
+                setattr(g, name, ptr(buf))
+        return g
+
+    def state(d, names, what):
+        for name in L.TEMPORAL_GBUFFER_STATE_NAMES:
+            if not isinstance(d, dict) or name not in d:
+                raise L.LrtError(L.LRT_E_INVALID, f"{what} lacks {name!r}")
+        st = L.TemporalState()
+        for name, buf in d.items():
+            if name not in names:
+                raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
+            if name in L.TEMPORAL_GBUFFER_STATE_NAMES:
+                check(buf, f"{what} {name}", name)
+                setattr(st, name, ptr(buf))
+        return st
+
+    gc = planes(cur, L.TEMPORAL_GBUFFER_CUR_NAMES, "cur")
+    gp = planes(prev_g, L.TEMPORAL_GBUFFER_PREV_NAMES, "prev_g") if prev_g is not None else None
+    # (a returned state, or an accumulator's, may be passed back as it is: only color and moment2 are read)
+    ps = state(prev, L.TEMPORAL_STATE_NAMES + ("color_std",), "prev") if prev is not None else None
+    if out is None:
+        out = {name: make() for name in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
+    ns = state(out, L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",), "out")
+    std = None
+    if "color_std" in out:
+        check(out["color_std"], "out color_std", "color_std")
+        std = ptr(out["color_std"])
+    L.check(entry(ctypes.c_void_p(ptr(color)), ctypes.byref(gc), ctypes.byref(gp) if gp is not None else None,
+                  ctypes.byref(ps) if ps is not None else None, ctypes.byref(ns),
+                  ctypes.c_void_p(std) if std else None, *extra))
+    return out
+
+
+def temporal_accumulate_gbuffer_host(color: np.ndarray, cur: dict, prev_g: Optional[dict], prev: Optional[dict],
+                                     out: Optional[dict] = None, **params) -> dict:
+    """One temporal accumulation step driven by the G-buffer, on host buffers
+    (lrt_temporal_accumulate_gbuffer_host). color: the current frame, float32 [height, width, 4] (or
+    flat with width=, height=); cur: its G-buffer {"normal", "motion", "id"[, ...]} as
+    gbuffer_host(id=True, motion=True) returns it at guide_scale 1 (id int32, the rest float32; the
+    other planes are not read); prev_g: the previous frame's G-buffer {"normal", "id"[, ...]} and
+    prev: the state {"color", "moment2"[, ...]} a previous call returned -- both, or None and None for
+    no history. out: the destination buffers {"color", "moment2"[, "color_std"]} (none may be an
+    input or a previous buffer; the alphas of color and color_std stay), default new zeroed ones.
+    params: cur_scale (the colour's only), alpha_min, normal_min, short_std, min_history. Returns the
+    new state (out)."""
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = temporal_gbuffer_desc(w, h, **params)
+
+    def check(buf, what, name):
+        n, dt = (w * h, np.int32) if name == "id" else (w * h * 4, np.float32)
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
+
+    return _temporal_gbuffer_call(lambda *a: L.lib().lrt_temporal_accumulate_gbuffer_host(ctypes.byref(d), *a), color,
+                                  cur, prev_g, prev, out, check, lambda b: b.ctypes.data,
+                                  lambda: np.zeros((h, w, 4), np.float32), ())
+
+
+def temporal_accumulate_gbuffer_tensor(color, cur: dict, prev_g: Optional[dict], prev: Optional[dict],
+                                       out: Optional[dict] = None, stream=None, **params) -> dict:
+    """temporal_accumulate_gbuffer_host on cuda tensors (lrt_temporal_accumulate_gbuffer_device):
+    asynchronous on `stream` (a torch.cuda.Stream, default: current) and ordered only against it.
+    "id" is an int32 tensor, the others float32. Returns the new state."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = temporal_gbuffer_desc(w, h, **params)
+    if not getattr(color, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {w * h * 4} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color.device)
+
+    def check(t, what, name):
+        n, dt = (w * h, torch.int32) if name == "id" else (w * h * 4, torch.float32)
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == dt
+                and t.is_contiguous() and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
+
+    def make():
+        with torch.cuda.stream(s):
+            return torch.zeros((h, w, 4), device=color.device)
+
+    return _temporal_gbuffer_call(lambda *a: L.lib().lrt_temporal_accumulate_gbuffer_device(ctypes.byref(d), *a),
+                                  color, cur, prev_g, prev, out, check, lambda t: t.data_ptr(), make,
+                                  (ctypes.c_void_p(s.cuda_stream),))
+
+
 class TemporalAccumulator:
     """The two ping-pong states of a width x height frame on `device`, the previous camera and, for
     a scene whose spheres move, the previous step's spheres: step() blends a freshly rendered frame
-    into the history and returns what the denoiser takes."""
+    into the history and returns what the denoiser takes. step_gbuffer() is the same step driven by a
+    G-buffer's ids and motion vectors; switching between the two forms, like reset(), drops the
+    history."""
 
     def __init__(self, width: int, height: int, device="cuda:0"):
         import torch
@@ -604,13 +721,16 @@ class TemporalAccumulator:
         self._states = [{n: torch.zeros((self.height, self.width, 4), device=self.device) for n in names}
                         for _ in range(2)]
         self._cur = 0            # the state the last step wrote
-        self._camera = None      # its camera (None: no history)
+        self._camera = None      # its camera (None: no history for step())
         self._spheres = None     # its scene, if it was given one
+        self._prev_g = None      # the last step_gbuffer's normal and id tensors (None: no history for step_gbuffer())
+        self._planes = [None, None]   # gbuffer_planes()'s two sets, allocated on first use
 
     def reset(self) -> None:
-        """Drop the history: the next step starts over (a new scene, a camera cut)."""
+        """Drop the history: the next step or step_gbuffer starts over (a new scene, a camera cut)."""
         self._camera = None
         self._spheres = None
+        self._prev_g = None
 
     def step(self, color, features: dict, camera: L.Camera, cur_scale: float = 1.0, stream=None, spheres=None,
              motion=None, **params):
@@ -622,7 +742,9 @@ class TemporalAccumulator:
         [count, 4]) where spheres move between steps: the step is then
         temporal_accumulate_moving_tensor against the previous step's scene (on the first step, after
         reset() and after a step without spheres the scene is its own predecessor), and `motion`, a
-        cuda tensor [height, width, 4], receives the motion vectors."""
+        cuda tensor [height, width, 4], receives the motion vectors. After a step_gbuffer() the
+        history is dropped: the two forms keep different states."""
+        self._prev_g = None
         cur = {k: v for k, v in features.items() if k in L.TEMPORAL_CUR_NAMES}
         unknown = [k for k in features if k not in L.FEATURE_NAMES]
         if unknown:
@@ -649,12 +771,56 @@ class TemporalAccumulator:
         self._camera = L.Camera.from_buffer_copy(camera)
         return nxt["color"], {k: nxt[k] for k in L.GUIDE_NAMES if k in out}
 
+    def step_gbuffer(self, color, gbuffer: dict, cur_scale: float = 1.0, stream=None, **params):
+        """One accumulation step driven by the G-buffer (temporal_accumulate_gbuffer_tensor) of the
+        frame `color` with its planes {"normal", "motion", "id"[, ...]} as gbuffer_tensor(id=True,
+        motion=True) fills them at guide_scale 1: no camera and no scene. Returns (color,
+        {"color_std": ...}), the accumulator's own tensors, valid until the step after the next; the
+        G-buffer's own normal, world_pos and albedo are the guides of denoise_tensor and
+        svgf_filter_tensor. The accumulator remembers the `normal` and `id` tensors by reference,
+        without copying: they are the next step's history, so they must stay as they are until it has
+        run, and handing the same tensors in again raises LRT_E_INVALID (ping-pong two sets:
+        gbuffer_planes()). Of `state` only color and moment2 are written. After a step() the history is
+        dropped: the two forms keep different states. params: alpha_min, normal_min, short_std,
+        min_history."""
+        if not isinstance(gbuffer, dict) or any(n not in gbuffer for n in L.TEMPORAL_GBUFFER_CUR_NAMES):
+            raise L.LrtError(L.LRT_E_INVALID, "gbuffer must hold normal, motion and id")
+        if self._prev_g is not None and any(gbuffer[n] is self._prev_g[n] for n in L.TEMPORAL_GBUFFER_PREV_NAMES):
+            raise L.LrtError(L.LRT_E_INVALID, "gbuffer's normal and id are the previous step's tensors: they are its "
+                                              "history (fill another set: gbuffer_planes())")
+        nxt = self._states[1 - self._cur]
+        out = {k: nxt[k] for k in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
+        prev = self._states[self._cur] if self._prev_g is not None else None
+        temporal_accumulate_gbuffer_tensor(color, gbuffer, self._prev_g, prev, out=out, stream=stream,
+                                           width=self.width, height=self.height, cur_scale=cur_scale, **params)
+        self._prev_g = {n: gbuffer[n] for n in L.TEMPORAL_GBUFFER_PREV_NAMES}
+        self._cur = 1 - self._cur
+        self._camera = None
+        self._spheres = None
+        return nxt["color"], {"color_std": nxt["color_std"]}
+
+    def gbuffer_planes(self) -> dict:
+        """The set of G-buffer planes to fill next, {"normal", "world_pos", "albedo", "motion", "id"}
+        (id int32 [height, width], the others float32 [height, width, 4]): one of two sets the
+        accumulator allocates on first use (uninitialised until filled), the one the last
+        step_gbuffer() does not hold as its history. Meant as gbuffer_tensor(..., out=acc.gbuffer_planes()),
+        whose result goes to step_gbuffer(): the caller ping-pongs without owning buffers."""
+        import torch
+
+        held = self._prev_g["normal"] if self._prev_g is not None else None
+        k = 1 if self._planes[0] is not None and held is self._planes[0]["normal"] else 0
+        if self._planes[k] is None:
+            self._planes[k] = {n: torch.empty((self.height, self.width) if n == "id" else (self.height, self.width, 4),
+                                              dtype=torch.int32 if n == "id" else torch.float32, device=self.device)
+                               for n in L.TEMPORAL_GBUFFER_PLANES}
+        return dict(self._planes[k])
+
     @property
     def state(self) -> dict:
         """The state the last step wrote, {"color", "moment2", "normal", "world_pos", "albedo"}: the
         accumulator's own tensors, valid until the step after the next; read-only (a new dict each
         time). svgf_filter_tensor(acc.state["color"], acc.state["moment2"], guides) chains on the
-        step's stream."""
+        step's stream. step_gbuffer() writes color and moment2 only."""
         return {k: self._states[self._cur][k] for k in L.TEMPORAL_STATE_NAMES}
 
 

@@ -12,13 +12,20 @@ output buffer once -- against which the same session's device-to-device copy mov
 (reads plus writes) is the yardstick; render_4spp_ms (the plain 4 spp render of the frame) and
 denoise_ms (the 5-pass denoise of the accumulated frame) are there for scale.
 
-  python tools/temporal_bench.py [--width W --height H --reps N --dtheta RAD] [--moving] [--images DIR]
+  python tools/temporal_bench.py [--width W --height H --reps N --dtheta RAD] [--moving] [--gbuffer] [--images DIR]
 
 --moving adds the step under moving spheres (lrt_temporal_accumulate_moving_device) on the same
 camera pair: moving_step_ms (the default scene, one sphere translated between the two frames, no
 motion output), moving_step_motion_ms (with it), moving_step_1000_ms (random_scene(1000, 1), no
 motion output) and moving_over_static = moving_step_ms / step_ms. Without the flag the line is the
 one it always was.
+
+--gbuffer adds the step driven by the G-buffer's ids and motion vectors
+(lrt_temporal_accumulate_gbuffer_device) on the same camera pair, its colours from the pool kernel:
+gbuffer_step_ms (the default scene, one sphere translated between the two frames),
+gbuffer_step_1000_ms (the same on random_scene(1000, 1)), gbuffer_pass_ms (the G-buffer call that
+feeds it: normal, world_pos, albedo, motion and id) and gbuffer_step_bytes; the line's step_ms, and
+the moving figures where --moving is given too, are the same session's.
 """
 import argparse
 import json
@@ -38,6 +45,9 @@ CUR = ("normal", "world_pos", "albedo")
 # frames -- the default scene without and with motion vectors, and random_scene(1000, 1) without
 MOVING_FIELDS = ("moving_step_ms", "moving_step_motion_ms", "moving_step_1000_ms")
 MOVING_STEP = 0.1
+# --gbuffer: the step driven by the G-buffer, and the pass that feeds it
+GBUFFER_FIELDS = ("gbuffer_step_ms", "gbuffer_step_1000_ms", "gbuffer_pass_ms")
+POOL = 512   # LRT_F_POOL
 
 
 def step_bytes(albedo=True, color_std=True):
@@ -46,6 +56,14 @@ def step_bytes(albedo=True, color_std=True):
     gather touches every history pixel about once); colour (12 B: its alpha stays), moment2, normal,
     world_pos (and albedo, 16 B each, and color_std, 12 B) written."""
     return 16 * (3 + albedo) + 16 * 4 + 12 + 16 * (3 + albedo) + 12 * color_std
+
+
+def gbuffer_step_bytes(color_std=True):
+    """Bytes per pixel the G-buffer step must move: the current colour, normal and motion (16 B each)
+    and id (4 B) read; the history's colour, moment2 and normal (16 B each) and id (4 B) read (a
+    bilinear gather touches every history pixel about once); colour (12 B: its alpha stays), moment2
+    (16 B) and color_std (12 B) written."""
+    return (16 * 3 + 4) + (16 * 3 + 4) + 12 + 16 + 12 * color_std
 
 
 def orbit_args(theta, w, h):
@@ -83,6 +101,8 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=40, help="timed repetitions (>= 20)")
     ap.add_argument("--moving", action="store_true",
                     help="also time lrt_temporal_accumulate_moving_device (the MOVING_FIELDS of the line)")
+    ap.add_argument("--gbuffer", action="store_true",
+                    help="also time lrt_temporal_accumulate_gbuffer_device and its G-buffer pass (the GBUFFER_FIELDS)")
     ap.add_argument("--images", metavar="DIR",
                     help="write the 1 spp, accumulated and accumulated-then-denoised frames of 16 orbit steps there")
     args = ap.parse_args(argv)
@@ -194,6 +214,62 @@ def main(argv=None):
                 line[name] = round(t["median"], 4)
                 line[name + "_spread"] = rnd(t)
             line["moving_over_static"] = round(t_mov["median"] / t_step["median"], 3)
+        if args.gbuffer:
+            planes = ("normal", "world_pos", "albedo", "motion", "id")
+
+            def gbuffer_leg(spheres, mats, moved):
+                """Median ms of the G-buffer step, of the five-plane pass that feeds it and of a
+                guides-only pass (what feeds the moving step), on the scene `spheres` whose sphere
+                `moved` came MOVING_STEP along x: the previous state is the previous scene's
+                pool-kernel frame from cam0."""
+                before = list(spheres)
+                c = before[moved].center
+                before[moved] = L.Sphere(L.f3(c.x - MOVING_STEP, c.y, c.z), before[moved].radius)
+
+                def pool(cam, t):
+                    with torch.cuda.stream(s):
+                        buf = frame()
+                    lrt.render_tensor(lrt.Job(width=w, height=h, frame0=t, frames=1, max_depth=args.depth, camera=cam,
+                                              flags=POOL), buf, rays, stream=s)
+                    return buf
+
+                lrt.set_scene(before, mats)
+                b0 = pool(cam0, 0)
+                g0 = lrt.gbuffer_tensor(w, h, cam0, id=True, motion=True, stream=s)
+                lrt.set_scene(spheres, mats)
+                b1 = pool(cam1, 1)
+                g1 = lrt.gbuffer_tensor(w, h, cam1, cam0, id=True, motion=True, prev_spheres=before, stream=s)
+                st = lrt.temporal_accumulate_gbuffer_tensor(b0, g0, None, None, stream=s, cur_scale=1.0)
+                out = {n: nxt[n] for n in ("color", "moment2", "color_std")}
+                s.synchronize()
+                t_st = timed(torch, s, lambda: lrt.temporal_accumulate_gbuffer_tensor(
+                    b1, g1, g0, st, out=out, stream=s, cur_scale=2.0), args.reps)
+                gout = {n: g1[n] for n in planes}
+                sph_a, before_a = (L.Sphere * len(before))(*spheres), (L.Sphere * len(before))(*before)   # marshalled once
+                t_gb = timed(torch, s, lambda: lrt.gbuffer_tensor(w, h, cam1, cam0, spheres=sph_a, prev_spheres=before_a,
+                                                                  out=gout, stream=s), args.reps)
+                guides = {n: g1[n] for n in ("normal", "world_pos", "albedo")}   # what the moving step takes
+                t_gd = timed(torch, s, lambda: lrt.gbuffer_tensor(w, h, cam1, out=guides, stream=s), args.reps)
+                s.synchronize()
+                return t_st, t_gb, t_gd, float((nxt["moment2"][..., 3] > 1.5).float().mean().item())
+
+            sph9, mat9 = lrt.default_scene()
+            sph1000, mat1000 = lrt.random_scene(1000, 1)
+            try:
+                t_g9, t_pass9, t_guides9, kept9 = gbuffer_leg(sph9, mat9, 2)
+                t_g1000, t_pass1000, t_guides1000, _ = gbuffer_leg(sph1000, mat1000, 500)
+            finally:
+                lrt.set_scene(sph9, mat9)
+            s.synchronize()
+            for name, t in zip(GBUFFER_FIELDS, (t_g9, t_g1000, t_pass9)):
+                line[name] = round(t["median"], 4)
+                line[name + "_spread"] = rnd(t)
+            line["gbuffer_pass_1000_ms"] = round(t_pass1000["median"], 4)
+            line["gbuffer_guides_ms"] = round(t_guides9["median"], 4)        # the three guides alone, for scale
+            line["gbuffer_guides_1000_ms"] = round(t_guides1000["median"], 4)
+            line["gbuffer_step_bytes"] = gbuffer_step_bytes()
+            line["gbuffer_history_kept"] = round(kept9, 4)
+            line["gbuffer_over_static"] = round(t_g9["median"] / t_step["median"], 3)
         if args.images:
             os.makedirs(args.images, exist_ok=True)
             steps = 16
