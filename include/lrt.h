@@ -826,6 +826,84 @@ int lrt_temporal_accumulate_gbuffer_host(const lrt_temporal_gbuffer_desc* desc, 
                                          const lrt_temporal_state* prev, const lrt_temporal_state* next,
                                          float* color_std);
 
+/* ---- G-buffer-guided upsampling of a low-resolution frame ------------------------- */
+
+/* Trace and filter at a fraction of the resolution, then reconstruct the full frame with the
+ * full-resolution G-buffer as guide: the G-buffer of lrt_gbuffer_* does not depend on who renders
+ * the colour or at what size, and gives exact pixel-centre ids and normals per pixel. f32, not
+ * bit-pinned (contraction allowed).
+ *
+ * Inputs. color_low: low_height rows of low_width RGBA quads (svgf_filter's output, say). low: the
+ * G-buffer of the low frame, high: the G-buffer of the output frame (width x height); of either,
+ * id and normal are required and albedo is optional, in both or in neither; the other members are
+ * ignored. Both come from the same camera at guide_scale 1 (unit normals).
+ * 1 <= low_width <= width <= 32768 and likewise the heights; the ratio need not be an integer and
+ * need not be the same on both axes.
+ *
+ * Per output pixel p = (x, y):
+ *  1. The taps. The position of p's centre in the low frame is found with integers, so that no
+ *     decision about which taps are used depends on rounding: a = (2x + 1) low_width - width (no
+ *     overflow of 32 bits under the size limit), X0 = floor(a / (2 width)), r = a - X0 2 width,
+ *     tx = (float)r / (float)(2 width), one IEEE division; Y0 and ty likewise. The four taps are
+ *     Q = (X0 + i, Y0 + j), i, j in {0, 1}, with the bilinear weight
+ *     b = (i ? tx : 1 - tx)(j ? ty : 1 - ty). A tap outside the low frame is skipped.
+ *  2. Class 0. A tap counts iff it is inside the frame and id_low(Q) = id_high(p); a miss matches
+ *     a miss (-1 = -1), and no id is ever used as an index. Its weight is w = b g, with
+ *     g = exp(-|N_low(Q) - N_high(p)|^2 / sigma_normal^2) for a hit and g = 1 for a miss.
+ *     sw = sum w. If sw >= weight_min: I = sum w c(Q) / sw.
+ *  3. Class 1, when sw < weight_min: a surface the four taps do not show is sought one ring
+ *     further out. Taps Q = (X0 - 1 + i, Y0 - 1 + j), i, j in 0..3,
+ *     w = k(i - 1 - tx) k(j - 1 - ty) g with k(d) = max(0, 1 - |d| / 2); the id rule and g as in
+ *     step 2. If that sum >= weight_min: I = sum w c(Q) / sum w.
+ *  4. Class 2, otherwise: plain bilinear, I = sum b c(Q) / sum b over the inside taps of step 1,
+ *     whatever their ids. At least one tap is inside, with b >= 1/4.
+ *  5. Albedo. With albedo planes, c(Q) = color_low(Q).rgb / max(A_low(Q), albedo_floor) per
+ *     channel where id_low(Q) >= 0, else color_low(Q).rgb; out = I max(A_high(p), albedo_floor)
+ *     where id_high(p) >= 0, else out = I. This is lrt_svgf's D: a silhouette pixel that falls to
+ *     class 2 still gets its own surface's albedo. Without albedo planes c = color_low.rgb and
+ *     out = I.
+ *  6. out.rgb is written, its alpha is left untouched. class_out (optional): width * height
+ *     int32 holding 0, 1 or 2. Flag LRT_UP_BILINEAR makes every pixel class 2: the baseline a
+ *     caller has without this stage. With it set the normals are not read and may be NULL.
+ * A tap that is skipped, does not count, or has weight 0 adds nothing to a sum, whatever its colour
+ * holds: a non-finite colour reaches only the pixels that give its tap a weight > 0.
+ *
+ * Limits: spheres only, first-hit guides only (reflections and refractions are upsampled with the
+ * mirror's own guides), whole frames, the first device. The normals are not anti-aliased at the
+ * output resolution: an edge pixel is one surface or the other. Tolerance-checked against its
+ * NumPy restatement (tests/upsample_ref.py); deterministic run to run. */
+#define LRT_UP_BILINEAR 1
+
+typedef struct lrt_upsample_desc {
+    int32_t width, height, low_width, low_height;
+    int32_t flags, reserved;                        /* LRT_UP_BILINEAR | 0 ; 0 */
+    float sigma_normal, albedo_floor, weight_min;   /* finite, > 0 */
+    int32_t reserved2;                              /* 0 */
+} lrt_upsample_desc;
+
+/* The defaults for a width x height frame from a low_width x low_height one: sigma_normal 0.3 and
+ * albedo_floor 0.01 (lrt_svgf's), weight_min 1e-3 (the temporal step's threshold on its sum of
+ * weights), flags 0. Choices taken from the neighbouring stages, not values tuned here. */
+int lrt_upsample_default(int width, int height, int low_width, int low_height, lrt_upsample_desc* out);
+
+/* The pass on device buffers. d_class may be NULL.
+ *
+ * LRT_E_INVALID, before any device use: NULL desc, d_color_low, d_low, d_high or d_out; a NULL id,
+ * or (without LRT_UP_BILINEAR) a NULL normal, in either G-buffer; sizes < 1, width or height >
+ * 32768, low_width > width, low_height > height, or width * height > INT_MAX / 4; an unknown flag
+ * bit; reserved or reserved2 != 0; sigma_normal, albedo_floor or weight_min not finite or <= 0;
+ * albedo in exactly one G-buffer; d_out or d_class overlapping an input or each other (by address
+ * range: the id planes and d_class are 4 bytes per pixel, the others 16, each sized by its own
+ * frame's dimensions). Then LRT_E_STATE without lrt_initialize(). Asynchronous on `stream` and
+ * ordered only against it, with no host round trip. Acts on the first device. */
+int lrt_upsample_device(const lrt_upsample_desc* desc, const float* d_color_low, const lrt_gbuffer* d_low,
+                        const lrt_gbuffer* d_high, float* d_out, int32_t* d_class, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_upsample_device's bit for bit (the alpha of out is the host buffer's own). */
+int lrt_upsample_host(const lrt_upsample_desc* desc, const float* color_low, const lrt_gbuffer* low,
+                      const lrt_gbuffer* high, float* out, int32_t* class_out);
+
 #ifdef __cplusplus
 }
 #endif

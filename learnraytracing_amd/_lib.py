@@ -190,6 +190,22 @@ TEMPORAL_GBUFFER_STATE_NAMES = ("color", "moment2")        # ... and reads or wr
 TEMPORAL_GBUFFER_PLANES = ("normal", "world_pos", "albedo", "motion", "id")   # TemporalAccumulator.gbuffer_planes()
 
 
+UP_BILINEAR = 1       # lrt_upsample_desc.flags: every pixel plain bilinear
+UP_MAX_SIZE = 32768
+
+
+class UpsampleDesc(ctypes.Structure):         # lrt_upsample_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("low_width", ctypes.c_int32), ("low_height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("sigma_normal", ctypes.c_float), ("albedo_floor", ctypes.c_float), ("weight_min", ctypes.c_float),
+                ("reserved2", ctypes.c_int32)]
+
+
+UPSAMPLE_PARAMS = ("sigma_normal", "albedo_floor", "weight_min", "flags")
+UPSAMPLE_NAMES = ("id", "normal", "albedo")   # what lrt_upsample_* reads of either G-buffer (albedo: both or neither)
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -258,6 +274,10 @@ SIGNATURES = {
     "lrt_temporal_accumulate_gbuffer_host": (_i, [_c.POINTER(TemporalGbufferDesc), _vp, _c.POINTER(Gbuffer),
                                                   _c.POINTER(Gbuffer), _c.POINTER(TemporalState),
                                                   _c.POINTER(TemporalState), _vp]),
+    "lrt_upsample_default": (_i, [_i, _i, _i, _i, _c.POINTER(UpsampleDesc)]),
+    "lrt_upsample_device": (_i, [_c.POINTER(UpsampleDesc), _vp, _c.POINTER(Gbuffer), _c.POINTER(Gbuffer), _vp, _vp,
+                                 _vp]),
+    "lrt_upsample_host": (_i, [_c.POINTER(UpsampleDesc), _vp, _c.POINTER(Gbuffer), _c.POINTER(Gbuffer), _vp, _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

@@ -16,6 +16,7 @@
 //   lrt_svgf.hip      the variance-guided filter over the temporal state (lrt_svgf_*): kernels and entry points
 //   lrt_tonemap.hip   auto-exposure metering and tone mapping (lrt_tonemap_*): kernels and entry points
 //   lrt_gbuffer.hip   the pixel-centre G-buffer pass (lrt_gbuffer_*): kernel and entry points
+//   lrt_upsample.hip  G-buffer-guided upsampling of a low-resolution frame (lrt_upsample_*): kernel and entry points
 //   lrt_atrous.h      the lattice tile of the two a-trous kernels (denoise, svgf): geometry, anchor, staging, taps
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
@@ -453,6 +454,22 @@ inline int validate_frame_size(int width, int height) {
 inline bool ranges_overlap(const void* p, size_t bytes_p, const void* q, size_t bytes_q) {
     const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
     return p && q && a < b + bytes_q && b < a + bytes_p;
+}
+// A buffer as the aliasing checks see it (p may be null: no buffer).
+struct Span {
+    const void* p;
+    size_t bytes;
+};
+// The outputs of a call against its inputs and each other: 0 none overlaps, 1 an output overlaps an
+// input, 2 two outputs overlap.
+inline int spans_alias(const Span* outs, int nout, const Span* ins, int nin) {
+    for (int i = 0; i < nout; ++i) {
+        for (int k = 0; k < nin; ++k)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, ins[k].p, ins[k].bytes)) return 1;
+        for (int j = i + 1; j < nout; ++j)
+            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return 2;
+    }
+    return 0;
 }
 // Context 0 is initialised (the caller holds g_mu).
 inline int require_initialized() {

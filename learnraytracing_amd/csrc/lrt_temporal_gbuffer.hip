@@ -95,11 +95,6 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_gbuffer_kernel(Temp
     }
 }
 
-struct Span {
-    const void* p;
-    size_t bytes;
-};
-
 // Everything that needs neither the library's state nor the device.
 static int validate_temporal_gbuffer(const lrt_temporal_gbuffer_desc* d, const float* color, const lrt_gbuffer* cur,
                                      const lrt_gbuffer* prev_g, const lrt_temporal_state* prev,
@@ -125,14 +120,9 @@ static int validate_temporal_gbuffer(const lrt_temporal_gbuffer_desc* d, const f
     const Span ins[8] = {{color, quad}, {cur->normal, quad}, {cur->motion, quad}, {cur->id, word},
                          {prev ? prev->color : nullptr, quad}, {prev ? prev->moment2 : nullptr, quad},
                          {prev_g ? prev_g->normal : nullptr, quad}, {prev_g ? prev_g->id : nullptr, word}};
-    for (int i = 0; i < 3; ++i) {
-        for (const Span& in : ins)
-            if (ranges_overlap(outs[i].p, outs[i].bytes, in.p, in.bytes))
-                return fail(LRT_E_INVALID, "aliasing: an output buffer overlaps an input or a prev buffer");
-        for (int j = i + 1; j < 3; ++j)
-            if (ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
-                return fail(LRT_E_INVALID, "aliasing: two output buffers overlap");
-    }
+    if (const int al = spans_alias(outs, 3, ins, 8))
+        return fail(LRT_E_INVALID, al == 1 ? "aliasing: an output buffer overlaps an input or a prev buffer"
+                                           : "aliasing: two output buffers overlap");
     // a G-buffer overwritten in place is no history
     if (prev_g)
         for (const Span& c : {ins[1], ins[3]})

@@ -1134,6 +1134,113 @@ def gbuffer_tensor(width: int, height: int, camera: L.Camera, prev_camera: Optio
                          spheres, prev_spheres, (ctypes.c_void_p(s.cuda_stream),))
 
 
+# ---- G-buffer-guided upsampling of a low-resolution frame -----------------------------------
+def upsample_desc(width: int, height: int, low_width: int, low_height: int, **params) -> L.UpsampleDesc:
+    """lrt_upsample_default for a width x height frame from a low_width x low_height one, with any of
+    sigma_normal, albedo_floor, weight_min, flags (UP_BILINEAR) overridden."""
+    d = L.UpsampleDesc()
+    L.check(L.lib().lrt_upsample_default(int(width), int(height), int(low_width), int(low_height), ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.UPSAMPLE_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown upsample parameter {name!r}")
+        setattr(d, name, int(v) if name == "flags" else float(v))
+    return d
+
+
+def _upsample_sizes(color_low, low, high):
+    """(width, height, low_width, low_height) from color_low [low_height, low_width, 4] and high's id
+    [height, width]."""
+    if len(getattr(color_low, "shape", ())) != 3 or color_low.shape[2] != 4:
+        raise L.LrtError(L.LRT_E_INVALID, "color_low must be [low_height, low_width, 4]")
+    for d, what in ((low, "low"), (high, "high")):
+        if not isinstance(d, dict) or "id" not in d:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must hold id")
+    if len(getattr(high["id"], "shape", ())) != 2:
+        raise L.LrtError(L.LRT_E_INVALID, "high id must be [height, width]")
+    return int(high["id"].shape[1]), int(high["id"].shape[0]), int(color_low.shape[1]), int(color_low.shape[0])
+
+
+def _upsample_call(entry, d, color_low, low, high, out, class_out, check, ptr, extra):
+    """The marshalling the host and tensor front ends share: check(buf, what, name, low) validates a
+    plane called `name` of the low or the output frame (int32 for "id" and "class", else float32
+    quads), ptr(buf) is its address."""
+    need = ("id",) if d.flags & L.UP_BILINEAR else ("id", "normal")
+    check(color_low, "color_low", "color", True)
+
+    def planes(g, what, is_low):
+        if any(n not in g for n in need):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must hold " + " and ".join(need))
+        s = L.Gbuffer()
+        for name, buf in g.items():
+            if name not in L.GBUFFER_NAMES:
+                raise L.LrtError(L.LRT_E_INVALID, f"unknown G-buffer plane {name!r}")
+            if name in L.UPSAMPLE_NAMES:      # a whole G-buffer may be passed as it is: the rest is not read
+                check(buf, f"{what} {name}", name, is_low)
+                setattr(s, name, ptr(buf))
+        return s
+
+    gl, gh = planes(low, "low", True), planes(high, "high", False)
+    check(out, "out", "out", False)
+    if class_out is not None:
+        check(class_out, "class_out", "class", False)
+    L.check(entry(ctypes.c_void_p(ptr(color_low)), ctypes.byref(gl), ctypes.byref(gh), ctypes.c_void_p(ptr(out)),
+                  ctypes.c_void_p(ptr(class_out)) if class_out is not None else None, *extra))
+    return out
+
+
+def upsample_host(color_low: np.ndarray, low: dict, high: dict, out: Optional[np.ndarray] = None,
+                  class_out: Optional[np.ndarray] = None, **params) -> np.ndarray:
+    """Upsample a low-resolution frame with the output frame's G-buffer as guide, on host buffers
+    (lrt_upsample_host). color_low: float32 [low_height, low_width, 4] (svgf_filter_host's output,
+    say); low and high: the G-buffers of the low and of the output frame as gbuffer_host(id=True)
+    returns them for the same camera at guide_scale 1, {"id", "normal"[, "albedo"][, ...]} (id int32
+    [height, width], the rest float32; albedo in both or in neither -- drop it from both for a plain
+    colour; the other planes are not read). The sizes are the arrays'. out: the destination, float32
+    of >= width * height * 4 elements (only its rgb is written), default a zeroed [height, width, 4];
+    class_out: int32 of >= width * height elements receiving each pixel's class (0: its own surface
+    among the four taps, 1: one ring further out, 2: plain bilinear). params: sigma_normal,
+    albedo_floor, weight_min, flags (UP_BILINEAR: every pixel class 2, no normals needed). Returns out."""
+    w, h, lw, lh = _upsample_sizes(color_low, low, high)
+    d = upsample_desc(w, h, lw, lh, **params)
+    if out is None:
+        out = np.zeros((h, w, 4), np.float32)
+
+    def check(buf, what, name, is_low):
+        n = (lw * lh if is_low else w * h) * (1 if name in ("id", "class") else 4)
+        dt = np.int32 if name in ("id", "class") else np.float32
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
+
+    return _upsample_call(lambda *a: L.lib().lrt_upsample_host(ctypes.byref(d), *a), d, color_low, low, high, out,
+                          class_out, check, lambda b: b.ctypes.data, ())
+
+
+def upsample_tensor(color_low, low: dict, high: dict, out=None, class_out=None, stream=None, **params):
+    """upsample_host on cuda tensors (lrt_upsample_device): asynchronous on `stream` (a
+    torch.cuda.Stream, default: current) and ordered only against it. "id" and class_out are int32
+    tensors, the others float32. Returns out."""
+    import torch
+
+    w, h, lw, lh = _upsample_sizes(color_low, low, high)
+    d = upsample_desc(w, h, lw, lh, **params)
+    if not getattr(color_low, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color_low must be a contiguous cuda float32 tensor of >= {lw * lh * 4} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color_low.device)
+    if out is None:
+        with torch.cuda.stream(s):
+            out = torch.zeros((h, w, 4), device=color_low.device)
+
+    def check(t, what, name, is_low):
+        n = (lw * lh if is_low else w * h) * (1 if name in ("id", "class") else 4)
+        dt = torch.int32 if name in ("id", "class") else torch.float32
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color_low.device and t.dtype == dt
+                and t.is_contiguous() and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
+
+    return _upsample_call(lambda *a: L.lib().lrt_upsample_device(ctypes.byref(d), *a), d, color_low, low, high, out,
+                          class_out, check, lambda t: t.data_ptr(), (ctypes.c_void_p(s.cuda_stream),))
+
+
 def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
     """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
     import torch
