@@ -904,6 +904,127 @@ int lrt_upsample_device(const lrt_upsample_desc* desc, const float* d_color_low,
 int lrt_upsample_host(const lrt_upsample_desc* desc, const float* color_low, const lrt_gbuffer* low,
                       const lrt_gbuffer* high, float* out, int32_t* class_out);
 
+/* ---- temporal upsampling: a full-resolution history from jittered low frames ------- */
+
+/* lrt_upsample_* cannot bring back what the low frame never sampled: a sphere smaller than a low
+ * pixel is simply not in it. This stage closes the gap the way TAAU and FSR 2 do: the low camera is
+ * shifted by a different sub-pixel offset each frame (lrt_camera_jitter), and the shifted frames are
+ * accumulated into a history kept at the OUTPUT resolution. Per output pixel it does what
+ * lrt_temporal_accumulate_gbuffer_* and lrt_upsample_* each do half of. f32, not bit-pinned
+ * (contraction allowed).
+ *
+ * The intended chain: render at the low size under the jittered camera; lrt_gbuffer_* at the low
+ * size (id, normal) under the same jittered camera; lrt_gbuffer_* at the output size (id, normal,
+ * motion) under the UNJITTERED camera, so that a static camera still gives zero motion and the
+ * history is never resampled; this step; lrt_svgf_* at the output size on the state it leaves.
+ *
+ * The jitter (jitter_x, jitter_y) is the low camera's shift in units of 1 / (2 width) resp.
+ * 1 / (2 height) of a LOW pixel: low pixel X of a frame under lrt_camera_jitter's camera has its
+ * centre at the continuous low coordinate X + 1/2 + jitter_x / (2 width).
+ *
+ * Per output pixel p = (x, y):
+ *  1. Low taps, in integers. a = (2x + 1) low_width - width - jitter_x, X0 = floor(a / (2 width))
+ *     (a true floor: a >= -2 width + 1, so X0 >= -1), r = a - X0 2 width,
+ *     tx = (float)r / (float)(2 width); Y0 and ty likewise. Everything fits 32 bits under the size
+ *     limit (the largest product is 65535 x 32768). The four taps are Q = (X0 + i, Y0 + j) with the
+ *     bilinear weight b of lrt_upsample step 1. Which taps are used never depends on rounding.
+ *  2. Current estimate. A tap counts iff it is inside the low frame, b > 0 and
+ *     id_low(Q) = id_cur(p); a miss matches a miss (-1 = -1), and no id is ever used as an index.
+ *     w = b g, with g = exp(-|N_low(Q) - N_cur(p)|^2 / sigma_normal^2) for a hit and g = 1 for a
+ *     miss. sw = sum w. The current frame SPEAKS for p iff sw >= weight_min; then
+ *     I = cur_scale sum w color_low(Q).rgb / sw, and its confidence is beta = sum w k(Q) / sw with
+ *     k(Q) = exp(-(dx^2 + dy^2) / (2 sigma_sample^2)), dx = (i - tx) width / low_width,
+ *     dy = (j - ty) height / low_height: the distance from p's centre to the tap's sample in OUTPUT
+ *     pixels. beta = 1 where a low sample sits on p's centre and falls off as the nearest sample of
+ *     p's surface recedes. A tap that is skipped, does not count or has weight 0 is kept out of
+ *     every sum by a select, not by a product with 0: a non-finite colour reaches only the pixels
+ *     that count its tap.
+ *  3. History. Steps 1 and 2 of lrt_temporal_accumulate_gbuffer_*, word for word, on the
+ *     full-size planes: d_cur supplies motion, id and normal, d_prev_g normal and id, d_prev color
+ *     and moment2. The history COUNTS iff its sum of weights exceeds 1e-3; then h = sum b c' / sum b,
+ *     m = sum b m2' / sum b per channel and n_h = sum b n' / sum b. As in that step, a tap that is
+ *     outside or refused gets the weight 0 and stays in the sums as a product: the select of step 2
+ *     is step 2's alone, and a non-finite value in d_prev reaches every pixel that gathers it.
+ *  4. Blend; the class is what class_out receives.
+ *     class 0, history and current: n = n_h + beta, alpha = max(beta / n, alpha_min beta),
+ *       color = (1 - alpha) h + alpha I, moment2 = (1 - alpha) m + alpha I^2. With beta = 1 this
+ *       is step 6 of lrt_temporal_* exactly. The maximum is fmaxf, which ignores a NaN: where beta
+ *       underflows to 0 over n_h = 0 (a sigma_sample far below the spacing of the samples, a history
+ *       of class-3 pixels), beta / n is 0 / 0, alpha is 0 and the history stays.
+ *     class 1, history only: color = h, moment2 = m, n = n_h. The pixel waits for a phase of the
+ *       jitter that samples its surface.
+ *     class 2, current only: color = I, moment2 = I^2, n = beta.
+ *     class 3, neither: color = cur_scale x the plain bilinear mean over the inside taps of step 1
+ *       with b > 0, whatever their ids (class 2 of lrt_upsample); moment2 its square, n = 0.
+ *  5. Step 7 of lrt_temporal_*, unchanged: color_std, or short_std where n < min_history (n may
+ *     now be fractional).
+ * Outputs: next->color rgb (alpha untouched), next->moment2 (rgb and n), color_std rgb (alpha
+ * untouched) if given, class_out (int32, width * height) if given. Nothing else is written.
+ *
+ * Limits: first-hit motion only. Under a moving camera the history is resampled bilinearly every
+ * step and softens, as in any TAA. moment2 takes the square of an INTERPOLATED current colour where
+ * no sample sits on the pixel, so the variance there is underestimated; lrt_svgf's spatial estimate
+ * covers short histories. No albedo demodulation: the id test already keeps the taps on the pixel's
+ * own sphere, and one sphere has one albedo. Spheres only, whole frames, the first device; all
+ * planes at guide_scale 1. Tolerance-checked against its NumPy restatement
+ * (tests/temporal_upsample_ref.py); deterministic run to run. */
+typedef struct lrt_temporal_upsample_desc {
+    int32_t width, height, low_width, low_height;   /* the limits of lrt_upsample_desc */
+    int32_t jitter_x, jitter_y;   /* the low camera's shift, in units of 1/(2 width) resp. 1/(2 height) of a LOW
+                                     pixel; |jitter_x| <= width, |jitter_y| <= height (half a low pixel) */
+    int32_t flags;                /* 0 */
+    int32_t min_history;          /* >= 1 */
+    float cur_scale;              /* finite, > 0: multiplies the COLOUR only */
+    float alpha_min;              /* in (0, 1] */
+    float normal_min;             /* in [-1, 1] */
+    float short_std;              /* finite, > 0 */
+    float sigma_normal, sigma_sample, weight_min;   /* finite, > 0 */
+    int32_t reserved;             /* 0 */
+} lrt_temporal_upsample_desc;
+
+/* The defaults: alpha_min 0.05, normal_min 0.9, min_history 4, short_std 1e3 and cur_scale 1
+ * (lrt_temporal_gbuffer_default's); sigma_normal 0.3 and weight_min 1e-3 (lrt_upsample_default's);
+ * sigma_sample 0.5 output pixels; jitter 0. Choices taken from the neighbouring stages, not values
+ * tuned here. */
+int lrt_temporal_upsample_default(int width, int height, int low_width, int low_height, lrt_temporal_upsample_desc* out);
+
+/* *out = *camera with lowerLeftCorner += (dx / low_width) horizontalVec + (dy / low_height)
+ * verticalVec, dx = jitter_x / (2 width) and dy = jitter_y / (2 height) in f32; every other member
+ * is unchanged. Touches no device and needs no lrt_initialize. LRT_E_INVALID on NULLs, sizes < 1 or
+ * > 32768, low > output, |jitter_x| > width or |jitter_y| > height. */
+int lrt_camera_jitter(const lrt_camera* camera, int width, int height, int low_width, int low_height,
+                      int jitter_x, int jitter_y, lrt_camera* out);
+
+/* One step on device buffers. d_color_low: the low frame's colour. d_low: its G-buffer under the
+ * JITTERED camera; id and normal are required. d_cur: the output frame's G-buffer under the
+ * unjittered camera; id, normal and motion are required. d_prev_g (normal, id), d_prev and d_next
+ * (color, moment2) as in lrt_temporal_accumulate_gbuffer_device: d_prev and d_prev_g are both NULL
+ * (no history: classes 2 and 3 only) or both given. d_color_std and d_class may be NULL.
+ *
+ * LRT_E_INVALID, before any device use: whatever lrt_temporal_accumulate_gbuffer_device and
+ * lrt_upsample_device refuse about the arguments they share (NULL required pointers; sizes < 1,
+ * width or height > 32768, low_width > width, low_height > height, width * height > INT_MAX / 4;
+ * flags or reserved != 0; min_history < 1; non-finite parameters; cur_scale, short_std,
+ * sigma_normal, sigma_sample or weight_min <= 0; alpha_min outside (0, 1]; normal_min outside
+ * [-1, 1]; exactly one of d_prev and d_prev_g); |jitter_x| > width or |jitter_y| > height;
+ * d_next->color, d_next->moment2, d_color_std or d_class overlapping an input, a previous buffer
+ * or each other (by address range: id planes and d_class are 4 bytes per pixel, the others 16,
+ * each sized by its own frame); d_cur->normal or d_cur->id overlapping d_prev_g's. Then LRT_E_STATE
+ * without lrt_initialize(). Asynchronous on `stream` and ordered only against it, with no host
+ * round trip. Acts on the first device. */
+int lrt_temporal_upsample_device(const lrt_temporal_upsample_desc* desc, const float* d_color_low,
+                                 const lrt_gbuffer* d_low, const lrt_gbuffer* d_cur, const lrt_gbuffer* d_prev_g,
+                                 const lrt_temporal_state* d_prev, const lrt_temporal_state* d_next,
+                                 float* d_color_std, int32_t* d_class, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_temporal_upsample_device's bit for bit (the alphas of next->color and color_std are the host
+ * buffers' own). */
+int lrt_temporal_upsample_host(const lrt_temporal_upsample_desc* desc, const float* color_low,
+                               const lrt_gbuffer* low, const lrt_gbuffer* cur, const lrt_gbuffer* prev_g,
+                               const lrt_temporal_state* prev, const lrt_temporal_state* next,
+                               float* color_std, int32_t* class_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,21 @@ UPSAMPLE_PARAMS = ("sigma_normal", "albedo_floor", "weight_min", "flags")
 UPSAMPLE_NAMES = ("id", "normal", "albedo")   # what lrt_upsample_* reads of either G-buffer (albedo: both or neither)
 
 
+class TemporalUpsampleDesc(ctypes.Structure):  # lrt_temporal_upsample_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("low_width", ctypes.c_int32), ("low_height", ctypes.c_int32),
+                ("jitter_x", ctypes.c_int32), ("jitter_y", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("min_history", ctypes.c_int32),
+                ("cur_scale", ctypes.c_float), ("alpha_min", ctypes.c_float), ("normal_min", ctypes.c_float),
+                ("short_std", ctypes.c_float), ("sigma_normal", ctypes.c_float), ("sigma_sample", ctypes.c_float),
+                ("weight_min", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+TEMPORAL_UPSAMPLE_PARAMS = ("cur_scale", "alpha_min", "normal_min", "short_std", "min_history", "sigma_normal",
+                            "sigma_sample", "weight_min", "jitter_x", "jitter_y")
+TEMPORAL_UPSAMPLE_LOW_NAMES = ("id", "normal")             # what lrt_temporal_upsample_* reads of d_low
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -278,6 +293,14 @@ SIGNATURES = {
     "lrt_upsample_device": (_i, [_c.POINTER(UpsampleDesc), _vp, _c.POINTER(Gbuffer), _c.POINTER(Gbuffer), _vp, _vp,
                                  _vp]),
     "lrt_upsample_host": (_i, [_c.POINTER(UpsampleDesc), _vp, _c.POINTER(Gbuffer), _c.POINTER(Gbuffer), _vp, _vp]),
+    "lrt_temporal_upsample_default": (_i, [_i, _i, _i, _i, _c.POINTER(TemporalUpsampleDesc)]),
+    "lrt_camera_jitter": (_i, [_c.POINTER(Camera), _i, _i, _i, _i, _i, _i, _c.POINTER(Camera)]),
+    "lrt_temporal_upsample_device": (_i, [_c.POINTER(TemporalUpsampleDesc), _vp, _c.POINTER(Gbuffer),
+                                          _c.POINTER(Gbuffer), _c.POINTER(Gbuffer), _c.POINTER(TemporalState),
+                                          _c.POINTER(TemporalState), _vp, _vp, _vp]),
+    "lrt_temporal_upsample_host": (_i, [_c.POINTER(TemporalUpsampleDesc), _vp, _c.POINTER(Gbuffer),
+                                        _c.POINTER(Gbuffer), _c.POINTER(Gbuffer), _c.POINTER(TemporalState),
+                                        _c.POINTER(TemporalState), _vp, _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

@@ -1241,6 +1241,239 @@ def upsample_tensor(color_low, low: dict, high: dict, out=None, class_out=None, 
                           class_out, check, lambda t: t.data_ptr(), (ctypes.c_void_p(s.cuda_stream),))
 
 
+# ---- temporal upsampling: a full-resolution history from jittered low frames -----------------
+def temporal_upsample_desc(width: int, height: int, low_width: int, low_height: int, **params) -> L.TemporalUpsampleDesc:
+    """lrt_temporal_upsample_default for a width x height frame from a low_width x low_height one,
+    with any of cur_scale, alpha_min, normal_min, short_std, min_history, sigma_normal, sigma_sample,
+    weight_min, jitter_x, jitter_y overridden."""
+    d = L.TemporalUpsampleDesc()
+    L.check(L.lib().lrt_temporal_upsample_default(int(width), int(height), int(low_width), int(low_height),
+                                                  ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.TEMPORAL_UPSAMPLE_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown temporal upsample parameter {name!r}")
+        setattr(d, name, int(v) if name in ("min_history", "jitter_x", "jitter_y") else float(v))
+    return d
+
+
+def jitter_camera(camera: L.Camera, width: int, height: int, low_width: int, low_height: int, jitter_x: int,
+                  jitter_y: int) -> L.Camera:
+    """The low frame's camera under the jitter (lrt_camera_jitter): `camera` with its lower left
+    corner shifted so that low pixel X has its centre at X + 1/2 + jitter_x / (2 width) (rows
+    likewise). Render the low frame and its G-buffer with it, and the output frame's G-buffer with
+    `camera` itself."""
+    if not isinstance(camera, L.Camera):
+        raise L.LrtError(L.LRT_E_INVALID, "camera must be a Camera struct")
+    out = L.Camera()
+    L.check(L.lib().lrt_camera_jitter(ctypes.byref(camera), int(width), int(height), int(low_width), int(low_height),
+                                      int(jitter_x), int(jitter_y), ctypes.byref(out)))
+    return out
+
+
+def jitter_phases(width: int, low_width: int, height: int, low_height: int):
+    """The jitters [(jitter_x, jitter_y), ...] that put a low sample on every output pixel centre, for
+    a whole-number ratio on either axis (R x R of them at ratio R; (-+low_width, -+low_height) at ratio
+    2): phase p of an axis is low (2p + 1 - R). Each step moves along both axes, so that a short run of
+    steps already covers either. Raises LRT_E_INVALID for another ratio."""
+    w, lw, h, lh = int(width), int(low_width), int(height), int(low_height)
+    if lw < 1 or lh < 1 or w % lw or h % lh or w < lw or h < lh:
+        raise L.LrtError(L.LRT_E_INVALID, "jitter_phases needs whole-number ratios width / low_width and height / low_height")
+    rx, ry = w // lw, h // lh
+    return [(lw * (2 * (k % rx) + 1 - rx), lh * (2 * ((k // rx + k % rx) % ry) + 1 - ry)) for k in range(rx * ry)]
+
+
+def _temporal_upsample_sizes(color_low, cur):
+    """(width, height, low_width, low_height) from color_low [low_height, low_width, 4] and cur's id
+    [height, width]."""
+    if len(getattr(color_low, "shape", ())) != 3 or color_low.shape[2] != 4:
+        raise L.LrtError(L.LRT_E_INVALID, "color_low must be [low_height, low_width, 4]")
+    if not isinstance(cur, dict) or "id" not in cur or len(getattr(cur["id"], "shape", ())) != 2:
+        raise L.LrtError(L.LRT_E_INVALID, "cur must hold id as [height, width]")
+    return int(cur["id"].shape[1]), int(cur["id"].shape[0]), int(color_low.shape[1]), int(color_low.shape[0])
+
+
+def _temporal_upsample_call(entry, color_low, low, cur, prev_g, prev, out, class_out, check, ptr, make, extra):
+    """The marshalling the host and tensor front ends share: check(buf, what, name, is_low) validates
+    a plane called `name` of the low or the output frame (int32 for "id" and "class", else float32
+    quads), ptr(buf) is its address, make() a zeroed output frame. Returns the new state."""
+    check(color_low, "color_low", "color", True)
+
+    def planes(d, need, what, is_low):
+        if not isinstance(d, dict) or any(n not in d for n in need):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must hold " + " and ".join(need))
+        g = L.Gbuffer()
+        for name, buf in d.items():
+            if name not in L.GBUFFER_NAMES:
+                raise L.LrtError(L.LRT_E_INVALID, f"unknown G-buffer plane {name!r}")
+            if name in need:                  # a whole G-buffer may be passed as it is: the rest is not read
+                check(buf, f"{what} {name}", name, is_low)
+                setattr(g, name, ptr(buf))
+        return g
+
+    def state(d, names, what):
+        for name in L.TEMPORAL_GBUFFER_STATE_NAMES:
+            if not isinstance(d, dict) or name not in d:
+                raise L.LrtError(L.LRT_E_INVALID, f"{what} lacks {name!r}")
+        st = L.TemporalState()
+        for name, buf in d.items():
+            if name not in names:
+                raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
+            if name in L.TEMPORAL_GBUFFER_STATE_NAMES:
+                check(buf, f"{what} {name}", name, False)
+                setattr(st, name, ptr(buf))
+        return st
+
+    gl = planes(low, L.TEMPORAL_UPSAMPLE_LOW_NAMES, "low", True)
+    gc = planes(cur, L.TEMPORAL_GBUFFER_CUR_NAMES, "cur", False)
+    gp = planes(prev_g, L.TEMPORAL_GBUFFER_PREV_NAMES, "prev_g", False) if prev_g is not None else None
+    ps = state(prev, L.TEMPORAL_STATE_NAMES + ("color_std",), "prev") if prev is not None else None
+    if out is None:
+        out = {name: make() for name in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
+    ns = state(out, L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",), "out")
+    std = None
+    if "color_std" in out:
+        check(out["color_std"], "out color_std", "color_std", False)
+        std = ptr(out["color_std"])
+    if class_out is not None:
+        check(class_out, "class_out", "class", False)
+    L.check(entry(ctypes.c_void_p(ptr(color_low)), ctypes.byref(gl), ctypes.byref(gc),
+                  ctypes.byref(gp) if gp is not None else None, ctypes.byref(ps) if ps is not None else None,
+                  ctypes.byref(ns), ctypes.c_void_p(std) if std else None,
+                  ctypes.c_void_p(ptr(class_out)) if class_out is not None else None, *extra))
+    return out
+
+
+def temporal_upsample_host(color_low: np.ndarray, low: dict, cur: dict, prev_g: Optional[dict], prev: Optional[dict],
+                           out: Optional[dict] = None, class_out: Optional[np.ndarray] = None, jitter=(0, 0),
+                           **params) -> dict:
+    """One temporal upsampling step on host buffers (lrt_temporal_upsample_host). color_low: the low
+    frame rendered under jitter_camera(camera, ..., *jitter), float32 [low_height, low_width, 4]; low:
+    its G-buffer {"id", "normal"[, ...]} under the same jittered camera; cur: the output frame's
+    G-buffer {"normal", "motion", "id"[, ...]} under `camera` itself, as gbuffer_host(id=True,
+    motion=True) returns it at guide_scale 1; prev_g {"normal", "id"[, ...]} and prev {"color",
+    "moment2"[, ...]}: the previous step's output-size G-buffer and the state it returned -- both, or
+    None and None for no history. The sizes are the arrays'. out: the destination buffers {"color",
+    "moment2"[, "color_std"]} at the output size (the alphas of color and color_std stay), default new
+    zeroed ones; class_out: int32 of >= width * height elements receiving each pixel's class (0: history
+    and current, 1: history only, 2: current only, 3: neither). params: cur_scale (the colour's only),
+    alpha_min, normal_min, short_std, min_history, sigma_normal, sigma_sample, weight_min. Returns the
+    new state (out)."""
+    w, h, lw, lh = _temporal_upsample_sizes(color_low, cur)
+    d = temporal_upsample_desc(w, h, lw, lh, jitter_x=jitter[0], jitter_y=jitter[1], **params)
+
+    def check(buf, what, name, is_low):
+        n = (lw * lh if is_low else w * h) * (1 if name in ("id", "class") else 4)
+        dt = np.int32 if name in ("id", "class") else np.float32
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
+
+    return _temporal_upsample_call(lambda *a: L.lib().lrt_temporal_upsample_host(ctypes.byref(d), *a), color_low, low,
+                                   cur, prev_g, prev, out, class_out, check, lambda b: b.ctypes.data,
+                                   lambda: np.zeros((h, w, 4), np.float32), ())
+
+
+def temporal_upsample_tensor(color_low, low: dict, cur: dict, prev_g: Optional[dict], prev: Optional[dict],
+                             out: Optional[dict] = None, class_out=None, jitter=(0, 0), stream=None, **params) -> dict:
+    """temporal_upsample_host on cuda tensors (lrt_temporal_upsample_device): asynchronous on `stream`
+    (a torch.cuda.Stream, default: current) and ordered only against it. "id" and class_out are int32
+    tensors, the others float32. Returns the new state."""
+    import torch
+
+    w, h, lw, lh = _temporal_upsample_sizes(color_low, cur)
+    d = temporal_upsample_desc(w, h, lw, lh, jitter_x=jitter[0], jitter_y=jitter[1], **params)
+    if not getattr(color_low, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color_low must be a contiguous cuda float32 tensor of >= {lw * lh * 4} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color_low.device)
+
+    def check(t, what, name, is_low):
+        n = (lw * lh if is_low else w * h) * (1 if name in ("id", "class") else 4)
+        dt = torch.int32 if name in ("id", "class") else torch.float32
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color_low.device and t.dtype == dt
+                and t.is_contiguous() and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
+
+    def make():
+        with torch.cuda.stream(s):
+            return torch.zeros((h, w, 4), device=color_low.device)
+
+    return _temporal_upsample_call(lambda *a: L.lib().lrt_temporal_upsample_device(ctypes.byref(d), *a), color_low, low,
+                                   cur, prev_g, prev, out, class_out, check, lambda t: t.data_ptr(), make,
+                                   (ctypes.c_void_p(s.cuda_stream),))
+
+
+class TemporalUpsampler:
+    """The two ping-pong states of a width x height history on `device`, fed by low_width x low_height
+    frames whose camera is shifted by a different jitter each step (jitter_phases, jitter_camera):
+    step() blends one low frame in and returns what svgf_filter_tensor takes at the output size."""
+
+    def __init__(self, width: int, height: int, low_width: int, low_height: int, device="cuda:0"):
+        import torch
+
+        self.width, self.height = int(width), int(height)
+        self.low_width, self.low_height = int(low_width), int(low_height)
+        if not (1 <= self.low_width <= self.width and 1 <= self.low_height <= self.height):
+            raise L.LrtError(L.LRT_E_INVALID, "invalid image size")
+        self.device = torch.device(device)
+        names = L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)
+        self._states = [{n: torch.zeros((self.height, self.width, 4), device=self.device) for n in names}
+                        for _ in range(2)]
+        self._cur = 0            # the state the last step wrote
+        self._prev_g = None      # the last step's normal and id tensors (None: no history)
+        self._planes = [None, None]   # gbuffer_planes()'s two sets, allocated on first use
+
+    def reset(self) -> None:
+        """Drop the history: the next step starts over (a new scene, a camera cut)."""
+        self._prev_g = None
+
+    def step(self, color_low, low_gbuffer: dict, gbuffer: dict, jitter=(0, 0), cur_scale: float = 1.0, class_out=None,
+             stream=None, **params):
+        """One step (temporal_upsample_tensor) of the low frame `color_low` rendered under
+        jitter_camera(camera, ..., *jitter), with its planes low_gbuffer {"id", "normal"[, ...]} under
+        the same jittered camera and the output frame's planes gbuffer {"normal", "motion", "id"[, ...]}
+        under `camera` itself. Returns (color, {"color_std": ...}), the upsampler's own tensors, valid
+        until the step after the next; the G-buffer's own normal, world_pos and albedo are the guides
+        of svgf_filter_tensor. The upsampler remembers gbuffer's `normal` and `id` tensors by reference,
+        without copying: they are the next step's history, and handing the same tensors in again raises
+        LRT_E_INVALID (ping-pong two sets: gbuffer_planes()). params: alpha_min, normal_min, short_std,
+        min_history, sigma_normal, sigma_sample, weight_min."""
+        if not isinstance(gbuffer, dict) or any(n not in gbuffer for n in L.TEMPORAL_GBUFFER_CUR_NAMES):
+            raise L.LrtError(L.LRT_E_INVALID, "gbuffer must hold normal, motion and id")
+        if self._prev_g is not None and any(gbuffer[n] is self._prev_g[n] for n in L.TEMPORAL_GBUFFER_PREV_NAMES):
+            raise L.LrtError(L.LRT_E_INVALID, "gbuffer's normal and id are the previous step's tensors: they are its "
+                                              "history (fill another set: gbuffer_planes())")
+        if tuple(getattr(color_low, "shape", ())) != (self.low_height, self.low_width, 4) or \
+                tuple(getattr(gbuffer["id"], "shape", ())) != (self.height, self.width):
+            raise L.LrtError(L.LRT_E_INVALID, "color_low must be [low_height, low_width, 4] and gbuffer id [height, width]")
+        nxt = self._states[1 - self._cur]
+        prev = self._states[self._cur] if self._prev_g is not None else None
+        temporal_upsample_tensor(color_low, low_gbuffer, gbuffer, self._prev_g, prev, out=dict(nxt), class_out=class_out,
+                                 jitter=jitter, stream=stream, cur_scale=cur_scale, **params)
+        self._prev_g = {n: gbuffer[n] for n in L.TEMPORAL_GBUFFER_PREV_NAMES}
+        self._cur = 1 - self._cur
+        return nxt["color"], {"color_std": nxt["color_std"]}
+
+    def gbuffer_planes(self) -> dict:
+        """The set of output-size G-buffer planes to fill next, {"normal", "world_pos", "albedo",
+        "motion", "id"}: one of two sets the upsampler allocates on first use (uninitialised until
+        filled), the one the last step() does not hold as its history
+        (TemporalAccumulator.gbuffer_planes)."""
+        import torch
+
+        held = self._prev_g["normal"] if self._prev_g is not None else None
+        k = 1 if self._planes[0] is not None and held is self._planes[0]["normal"] else 0
+        if self._planes[k] is None:
+            self._planes[k] = {n: torch.empty((self.height, self.width) if n == "id" else (self.height, self.width, 4),
+                                              dtype=torch.int32 if n == "id" else torch.float32, device=self.device)
+                               for n in L.TEMPORAL_GBUFFER_PLANES}
+        return dict(self._planes[k])
+
+    @property
+    def state(self) -> dict:
+        """The state the last step wrote, {"color", "moment2"}: the upsampler's own tensors, valid until
+        the step after the next; read-only (a new dict each time)."""
+        return {k: self._states[self._cur][k] for k in L.TEMPORAL_GBUFFER_STATE_NAMES}
+
+
 def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
     """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
     import torch
