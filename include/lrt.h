@@ -1025,6 +1025,98 @@ int lrt_temporal_upsample_host(const lrt_temporal_upsample_desc* desc, const flo
                                const lrt_temporal_state* prev, const lrt_temporal_state* next,
                                float* color_std, int32_t* class_out);
 
+/* ---- history rectification: the state held to the frame's local range -------------- */
+
+/* The temporal stages above accept a history tap whenever its id (and normal) agree. Where a shadow
+ * crosses a floor, a light is dimmed or a mirror shows something that moved, ids and normals stay,
+ * and the stale colour decays at alpha_min per frame. This stage is the correction that TAA variance
+ * clipping, ReLAX history clamping and FSR 2 share: the local mean and standard deviation of a
+ * reference frame, the history clamped into that range, and the history length shortened where the
+ * clamp had to move it, so that it re-converges at 1/n instead of alpha_min. It reads and writes the
+ * (color, moment2) state that lrt_temporal_accumulate_gbuffer_* and lrt_temporal_upsample_* leave.
+ * f32, not bit-pinned (contraction allowed).
+ *
+ * Buffers. ref: a whole frame of RGBA quads at the state's resolution: the current frame's colour
+ * (the intended use, with ref_scale = the step's cur_scale), a faster history, or an upsampled low
+ * frame. id: the current G-buffer's id plane. Of state and out only color and moment2 are required
+ * and touched.
+ *
+ * Per pixel p, with i = id(p), r(q) = ref_scale ref(q).rgb, K = r(p), c and M the state's color and
+ * moment2 rgb and n moment2's alpha:
+ *  1. Window. q = p + (dx, dy), |dx|, |dy| <= radius. A tap counts iff it lies inside the image and
+ *     id(q) = i; the centre always counts, a miss matches a miss (-1 = -1), and no id is ever used
+ *     as an index. m is the count. Per channel the sums are taken about the pixel's own reference
+ *     value, so that nothing cancels against K: S1 = sum (r(q) - K), S2 = sum (r(q) - K)^2 over the
+ *     counting taps. A tap that does not count is kept out by a select, not by a product with 0: a
+ *     non-finite reference value reaches only the pixels that count its tap. a = S1 / m, mu = K + a,
+ *     sigma = sqrt(max(S2 / m - a^2, 0)).
+ *  2. Support. The pixel is supported iff m >= min_taps. An unsupported pixel passes c, M and n
+ *     through bit for bit; its class is 2.
+ *  3. Box. lo = mu - gamma sigma, hi = mu + gamma sigma; per channel c' = fminf(fmaxf(c, lo), hi).
+ *  4. History. Per channel moved = (c' != c), d = |c' - c|, t = d / (d + gamma sigma + range_floor);
+ *     e = (the largest t of the three)^2; n' = n + e (min(n, reset_history) - n). On a moved channel
+ *     M' = c'^2 + max(M - c^2, 0): the variance is kept and the mean shifted; M' = M on a channel
+ *     that did not move. The class is 1 if any channel moved, else 0; a class-0 pixel comes out bit
+ *     for bit as it went in (e = 0 exactly). The square in e makes a rounding-sized overshoot cost
+ *     nothing and a large one the whole history.
+ *  5. Step 7 of lrt_temporal_*, unchanged, on c', M' and n': color_std, or short_std where
+ *     n' < min_history.
+ * Outputs: out->color rgb (alpha untouched), out->moment2 (rgb and n'), color_std rgb (alpha
+ * untouched) if given, class_out (int32, width * height) if given. Nothing else is written.
+ *
+ * A non-finite value in the state is that pixel's own affair: what it gives there is unspecified,
+ * and it never reaches another pixel, because the state is read at p only.
+ *
+ * Limits: the box comes from a noisy reference: it is wide where the frame is noisy and catches
+ * large changes first. A surface with fewer than min_taps pixels of its id in the window is not
+ * rectified. The clamp is per RGB channel, with no YCoCg transform. Whole frames only, the first
+ * device, spheres only (the ids are lrt_gbuffer_*'s). Not measured: other references (a fast
+ * history), the effect on lrt_svgf's variance estimate, a moving camera. Tolerance-checked against
+ * its NumPy restatement (tests/rectify_ref.py); deterministic run to run. */
+#define LRT_RECTIFY_MAX_RADIUS 3
+typedef struct lrt_rectify_desc {      /* 48 bytes */
+    int32_t width, height;             /* a whole frame */
+    int32_t radius;                    /* 1..LRT_RECTIFY_MAX_RADIUS: the window is (2 radius + 1)^2 */
+    int32_t min_taps;                  /* 1..(2 radius + 1)^2 */
+    int32_t min_history;               /* >= 1: color_std's, step 7 of lrt_temporal_* */
+    int32_t flags;                     /* 0 */
+    float ref_scale;                   /* finite, > 0: multiplies the reference only (cur_scale's role) */
+    float gamma;                       /* finite, >= 0: the box is mean +- gamma sigma */
+    float range_floor;                 /* finite, > 0 */
+    float reset_history;               /* finite, >= 0 */
+    float short_std;                   /* finite, > 0 */
+    int32_t reserved;                  /* 0 */
+} lrt_rectify_desc;
+
+/* The defaults: radius 2, min_taps 5, gamma 1, range_floor 1e-4, reset_history 1, ref_scale 1;
+ * min_history 4 and short_std 1e3 (lrt_temporal_gbuffer_default's). Choices in the range the
+ * techniques named above use, not values tuned here. */
+int lrt_temporal_rectify_default(int width, int height, lrt_rectify_desc* out);
+
+/* One call on device buffers. d_color_std and d_class may be NULL.
+ *
+ * Aliasing: d_out->color may equal d_state->color and d_out->moment2 may equal d_state->moment2,
+ * exactly (in place), each independently. Otherwise no output may overlap an input or another
+ * output, by address range (the id and class planes are width * height * 4 bytes, the others 16
+ * bytes per pixel); d_ref and d_id may never overlap an output.
+ *
+ * LRT_E_INVALID, before any device use: NULL required pointers; sizes < 1 or width * height >
+ * INT_MAX / 4; radius outside 1..LRT_RECTIFY_MAX_RADIUS; min_taps outside 1..(2 radius + 1)^2;
+ * min_history < 1; flags or reserved != 0; non-finite parameters; ref_scale, range_floor or
+ * short_std <= 0; gamma or reset_history < 0; aliasing other than the above. Then LRT_E_STATE
+ * without lrt_initialize(). Asynchronous on `stream` and ordered only against it, with no host
+ * round trip and no scratch. Acts on the first device. */
+int lrt_temporal_rectify_device(const lrt_rectify_desc* desc, const float* d_ref, const int32_t* d_id,
+                                const lrt_temporal_state* d_state, const lrt_temporal_state* d_out,
+                                float* d_color_std, int32_t* d_class, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_temporal_rectify_device's bit for bit (the alphas of out->color and color_std are the host
+ * buffers' own). */
+int lrt_temporal_rectify_host(const lrt_rectify_desc* desc, const float* ref, const int32_t* id,
+                              const lrt_temporal_state* state, const lrt_temporal_state* out,
+                              float* color_std, int32_t* class_out);
+
 #ifdef __cplusplus
 }
 #endif

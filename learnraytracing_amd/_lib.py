@@ -221,6 +221,22 @@ TEMPORAL_UPSAMPLE_PARAMS = ("cur_scale", "alpha_min", "normal_min", "short_std",
 TEMPORAL_UPSAMPLE_LOW_NAMES = ("id", "normal")             # what lrt_temporal_upsample_* reads of d_low
 
 
+RECTIFY_MAX_RADIUS = 3
+
+
+class RectifyDesc(ctypes.Structure):          # lrt_rectify_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("radius", ctypes.c_int32), ("min_taps", ctypes.c_int32),
+                ("min_history", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("ref_scale", ctypes.c_float), ("gamma", ctypes.c_float), ("range_floor", ctypes.c_float),
+                ("reset_history", ctypes.c_float), ("short_std", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+RECTIFY_PARAMS = ("radius", "min_taps", "min_history", "ref_scale", "gamma", "range_floor", "reset_history",
+                  "short_std")
+RECTIFY_INT_PARAMS = ("radius", "min_taps", "min_history")
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -301,6 +317,11 @@ SIGNATURES = {
     "lrt_temporal_upsample_host": (_i, [_c.POINTER(TemporalUpsampleDesc), _vp, _c.POINTER(Gbuffer),
                                         _c.POINTER(Gbuffer), _c.POINTER(Gbuffer), _c.POINTER(TemporalState),
                                         _c.POINTER(TemporalState), _vp, _vp]),
+    "lrt_temporal_rectify_default": (_i, [_i, _i, _c.POINTER(RectifyDesc)]),
+    "lrt_temporal_rectify_device": (_i, [_c.POINTER(RectifyDesc), _vp, _vp, _c.POINTER(TemporalState),
+                                         _c.POINTER(TemporalState), _vp, _vp, _vp]),
+    "lrt_temporal_rectify_host": (_i, [_c.POINTER(RectifyDesc), _vp, _vp, _c.POINTER(TemporalState),
+                                       _c.POINTER(TemporalState), _vp, _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

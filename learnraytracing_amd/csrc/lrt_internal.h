@@ -18,6 +18,7 @@
 //   lrt_gbuffer.hip   the pixel-centre G-buffer pass (lrt_gbuffer_*): kernel and entry points
 //   lrt_upsample.hip  G-buffer-guided upsampling of a low-resolution frame (lrt_upsample_*): kernel and entry points
 //   lrt_temporal_upsample.hip  a full-resolution history from jittered low frames (lrt_temporal_upsample_*, lrt_camera_jitter)
+//   lrt_rectify.hip   history rectification (lrt_temporal_rectify_*): the LDS-tiled window kernel and entry points
 //   lrt_atrous.h      the lattice tile of the two a-trous kernels (denoise, svgf): geometry, anchor, staging, taps
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)

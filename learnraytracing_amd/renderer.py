@@ -703,6 +703,109 @@ def temporal_accumulate_gbuffer_tensor(color, cur: dict, prev_g: Optional[dict],
                                   (ctypes.c_void_p(s.cuda_stream),))
 
 
+# ---- history rectification -----------------------------------------------------------------
+def temporal_rectify_desc(width: int, height: int, **params) -> L.RectifyDesc:
+    """lrt_temporal_rectify_default for a width x height frame, with any of radius, min_taps,
+    min_history, ref_scale, gamma, range_floor, reset_history, short_std overridden."""
+    d = L.RectifyDesc()
+    L.check(L.lib().lrt_temporal_rectify_default(int(width), int(height), ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.RECTIFY_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown rectify parameter {name!r}")
+        setattr(d, name, int(v) if name in L.RECTIFY_INT_PARAMS else float(v))
+    return d
+
+
+def _temporal_rectify_call(entry, ref, ids, state, out, class_out, check, ptr, make, extra):
+    """The argument marshalling the host and tensor front ends share (see _temporal_gbuffer_call).
+    Returns the rectified state."""
+    check(ref, "ref", "ref")
+    check(ids, "id", "id")
+
+    def buffers(d, names, what):
+        for name in L.TEMPORAL_GBUFFER_STATE_NAMES:
+            if not isinstance(d, dict) or name not in d:
+                raise L.LrtError(L.LRT_E_INVALID, f"{what} lacks {name!r}")
+        st = L.TemporalState()
+        for name, buf in d.items():
+            if name not in names:
+                raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
+            if name in L.TEMPORAL_GBUFFER_STATE_NAMES:
+                check(buf, f"{what} {name}", name)
+                setattr(st, name, ptr(buf))
+        return st
+
+    # (a returned state, or an accumulator's, may be passed as it is: only color and moment2 are read)
+    ss = buffers(state, L.TEMPORAL_STATE_NAMES + ("color_std",), "state")
+    if out is None:
+        out = {name: make() for name in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
+    # out=state is in place: the state's other members are left alone (its color_std, if any, is refreshed)
+    ns = buffers(out, (L.TEMPORAL_STATE_NAMES if out is state else L.TEMPORAL_GBUFFER_STATE_NAMES) + ("color_std",), "out")
+    std = cls = None
+    if "color_std" in out:
+        check(out["color_std"], "out color_std", "color_std")
+        std = ptr(out["color_std"])
+    if class_out is not None:
+        check(class_out, "class_out", "id")
+        cls = ptr(class_out)
+    L.check(entry(ctypes.c_void_p(ptr(ref)), ctypes.c_void_p(ptr(ids)), ctypes.byref(ss), ctypes.byref(ns),
+                  ctypes.c_void_p(std) if std else None, ctypes.c_void_p(cls) if cls else None, *extra))
+    return out
+
+
+def temporal_rectify_host(ref: np.ndarray, id: np.ndarray, state: dict, out: Optional[dict] = None,
+                          class_out: Optional[np.ndarray] = None, **params) -> dict:
+    """Hold a temporal state to the local range of a reference frame, on host buffers
+    (lrt_temporal_rectify_host). ref: float32 [height, width, 4] (or flat with width=, height=), the
+    current frame's colour with ref_scale = the step's cur_scale, or any frame at the state's size;
+    id: the current G-buffer's int32 [height, width] id plane; state: {"color", "moment2"[, ...]} as a
+    temporal step returned it. out: the destination buffers {"color", "moment2"[, "color_std"]}; out=state
+    rectifies in place; otherwise none may be an input (the alphas of color and color_std stay);
+    default new zeroed ones. class_out: int32 [height, width], receives 0 (inside the box), 1
+    (clamped) or 2 (fewer than min_taps pixels of its id in the window: passed through). params:
+    radius, min_taps, min_history, ref_scale, gamma, range_floor, reset_history, short_std. Returns
+    the rectified state (out)."""
+    params = dict(params)
+    w, h = _frame_size(ref, params)
+    d = temporal_rectify_desc(w, h, **params)
+
+    def check(buf, what, name):
+        n, dt = (w * h, np.int32) if name == "id" else (w * h * 4, np.float32)
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
+
+    return _temporal_rectify_call(lambda *a: L.lib().lrt_temporal_rectify_host(ctypes.byref(d), *a), ref, id, state, out,
+                                  class_out, check, lambda b: b.ctypes.data, lambda: np.zeros((h, w, 4), np.float32), ())
+
+
+def temporal_rectify_tensor(ref, id, state: dict, out: Optional[dict] = None, class_out=None, stream=None,
+                            **params) -> dict:
+    """temporal_rectify_host on cuda tensors (lrt_temporal_rectify_device): asynchronous on `stream`
+    (a torch.cuda.Stream, default: current) and ordered only against it. id and class_out are int32
+    tensors, the others float32. Returns the rectified state."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(ref, params)
+    d = temporal_rectify_desc(w, h, **params)
+    if not getattr(ref, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"ref must be a contiguous cuda float32 tensor of >= {w * h * 4} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
+
+    def check(t, what, name):
+        n, dt = (w * h, torch.int32) if name == "id" else (w * h * 4, torch.float32)
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == ref.device and t.dtype == dt
+                and t.is_contiguous() and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
+
+    def make():
+        with torch.cuda.stream(s):
+            return torch.zeros((h, w, 4), device=ref.device)
+
+    return _temporal_rectify_call(lambda *a: L.lib().lrt_temporal_rectify_device(ctypes.byref(d), *a), ref, id, state,
+                                  out, class_out, check, lambda t: t.data_ptr(), make, (ctypes.c_void_p(s.cuda_stream),))
+
+
 class TemporalAccumulator:
     """The two ping-pong states of a width x height frame on `device`, the previous camera and, for
     a scene whose spheres move, the previous step's spheres: step() blends a freshly rendered frame
@@ -771,7 +874,8 @@ class TemporalAccumulator:
         self._camera = L.Camera.from_buffer_copy(camera)
         return nxt["color"], {k: nxt[k] for k in L.GUIDE_NAMES if k in out}
 
-    def step_gbuffer(self, color, gbuffer: dict, cur_scale: float = 1.0, stream=None, **params):
+    def step_gbuffer(self, color, gbuffer: dict, cur_scale: float = 1.0, stream=None, rectify: Optional[dict] = None,
+                     **params):
         """One accumulation step driven by the G-buffer (temporal_accumulate_gbuffer_tensor) of the
         frame `color` with its planes {"normal", "motion", "id"[, ...]} as gbuffer_tensor(id=True,
         motion=True) fills them at guide_scale 1: no camera and no scene. Returns (color,
@@ -782,9 +886,20 @@ class TemporalAccumulator:
         run, and handing the same tensors in again raises LRT_E_INVALID (ping-pong two sets:
         gbuffer_planes()). Of `state` only color and moment2 are written. After a step() the history is
         dropped: the two forms keep different states. params: alpha_min, normal_min, short_std,
-        min_history."""
+        min_history. rectify: None, or a dict of temporal_rectify_tensor's parameters (possibly empty):
+        the step is then followed on the same stream by temporal_rectify_tensor in place on the state
+        just written, with `color` as the reference, gbuffer's id, ref_scale = cur_scale and the
+        step's own min_history and short_std (unless the dict sets them); color_std is refreshed."""
         if not isinstance(gbuffer, dict) or any(n not in gbuffer for n in L.TEMPORAL_GBUFFER_CUR_NAMES):
             raise L.LrtError(L.LRT_E_INVALID, "gbuffer must hold normal, motion and id")
+        rp = None
+        if rectify is not None:
+            if not isinstance(rectify, dict):
+                raise L.LrtError(L.LRT_E_INVALID, "rectify must be None or a dict of temporal_rectify_tensor's parameters")
+            rp = {k: params[k] for k in ("min_history", "short_std") if k in params}
+            rp.update(ref_scale=cur_scale)
+            rp.update(rectify)
+            temporal_rectify_desc(self.width, self.height, **rp)     # an unknown name raises before the step runs
         if self._prev_g is not None and any(gbuffer[n] is self._prev_g[n] for n in L.TEMPORAL_GBUFFER_PREV_NAMES):
             raise L.LrtError(L.LRT_E_INVALID, "gbuffer's normal and id are the previous step's tensors: they are its "
                                               "history (fill another set: gbuffer_planes())")
@@ -793,6 +908,9 @@ class TemporalAccumulator:
         prev = self._states[self._cur] if self._prev_g is not None else None
         temporal_accumulate_gbuffer_tensor(color, gbuffer, self._prev_g, prev, out=out, stream=stream,
                                            width=self.width, height=self.height, cur_scale=cur_scale, **params)
+        if rp is not None:
+            temporal_rectify_tensor(color, gbuffer["id"], out, out=out, stream=stream, width=self.width,
+                                    height=self.height, **rp)
         self._prev_g = {n: gbuffer[n] for n in L.TEMPORAL_GBUFFER_PREV_NAMES}
         self._cur = 1 - self._cur
         self._camera = None
@@ -1404,7 +1522,10 @@ def temporal_upsample_tensor(color_low, low: dict, cur: dict, prev_g: Optional[d
 class TemporalUpsampler:
     """The two ping-pong states of a width x height history on `device`, fed by low_width x low_height
     frames whose camera is shifted by a different jitter each step (jitter_phases, jitter_camera):
-    step() blends one low frame in and returns what svgf_filter_tensor takes at the output size."""
+    step() blends one low frame in and returns what svgf_filter_tensor takes at the output size.
+    There is no rectify= here: the low frame is not at the state's size. The state can be handed to
+    temporal_rectify_tensor(ref, gbuffer["id"], state, out=state) with a full-size reference the caller
+    makes (upsample_tensor of the low frame, say)."""
 
     def __init__(self, width: int, height: int, low_width: int, low_height: int, device="cuda:0"):
         import torch
