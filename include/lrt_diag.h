@@ -39,6 +39,14 @@ int lrt_libm_eval_device(int kind, const float* d_in, float* d_out, long long n)
 int lrt_exact_div_sweep(int what, unsigned long long first, unsigned long long count, int on_device,
                         unsigned long long* out);
 
+/* The one-rounding forms of the RNG's floats (lrt_trace.h: rng_signed, rng_angle, rng_offset,
+ * rng_one_minus) against the reference's expressions on R = RandomFloat01, for every draw integer
+ * k in [0, 2^24). out[12]: mismatches of 0: 2 R - 1 (both operand orders), 1: R * 2 * kPI,
+ * 2: 2 * kPI * R, 3: 1 - R, 4..10: (float)x + R for x = 0, 1, 2, 3, 1279, 4095, 7679; out[11]:
+ * the draws swept (2^24). Every count must be 0. on_device = 0: the host build (hardware fma
+ * where the CPU has it, several threads); otherwise one launch on the current device. Blocking. */
+int lrt_rng_form_sweep(int on_device, unsigned long long* out);
+
 /* BVH diagnostics (host only, no GPU): build the BVH of the given scene and trace n rays
  * (6 floats each: origin, direction) with the device traversal code. out[7]: mean nodes
  * visited, mean spheres tested, max nodes, max spheres, mismatches per ray against the
@@ -76,6 +84,13 @@ int lrt_accel_eval(const lrt_sphere* spheres, int count, const float* rays, int 
 int lrt_scatter_eval(const lrt_sphere* spheres, const lrt_material* materials, int count,
                      const int* ids, const float* rays, const float* recs, const uint32_t* seeds,
                      int n, float* out, int* ret, int* counted, uint32_t* state, int on_device);
+
+/* Test hook: later pool-kernel launches take tiles of `pix` pixels (16, 32, 64, 128 or 256) wherever
+ * a round of the launch's frames fits such a tile (pix * frames <= 4096), whatever the window's
+ * size and the other stream's state; 0 restores the library's policy. 128- and 256-px tiles are
+ * otherwise chosen only for a launch that overlaps another stream's and has a tile per resident
+ * wave, which no small window reaches. */
+int lrt_pool_force_pix(int pix);
 
 /* ---- kernel timing (bench.py's launch-alone leg) ------------------------------- */
 /* on != 0: every later render kernel launch (the pool kernel and v0), on whichever device it

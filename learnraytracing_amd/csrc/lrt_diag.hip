@@ -129,6 +129,36 @@ __global__ __launch_bounds__(256) void exact_div_kernel(int what, unsigned long 
     if (c[3] != ~0ull) atomicMin(&out[3], c[3]);
 }
 
+// ---- lrt_rng_form_sweep: the one-rounding forms of the RNG's floats (lrt_trace.h) -----------
+// Draw integer k (kf = (float)k, exact): each source expression, written as the reference has it
+// from R = RandomFloat01's kf * 2^-24, against the form the kernels evaluate. c[form]: mismatches.
+constexpr int kRngForms = 4, kRngCamX = 7;
+LRT_HD void rng_form_case(uint32_t k, unsigned long long* c) {
+    const float kf = (float)(k & 0xFFFFFFu);
+    const float R = kf * (1.0f / 16777216.0f);   // RandomFloat01
+    const float camx[kRngCamX] = {0.0f, 1.0f, 2.0f, 3.0f, 1279.0f, 4095.0f, 7679.0f};
+    if (!same_bits(R * 2.0f - 1.0f, rng_signed(kf))) ++c[0];            // RandomUnitVector's z
+    if (!same_bits(2.0f * R - 1.0f, rng_signed(kf))) ++c[0];            // the rejection candidates
+    if (!same_bits(R * 2.0f * kPI, rng_angle(kf))) ++c[1];              // RandomUnitVector's a
+    if (!same_bits(2.0f * kPI * R, rng_angle(kf))) ++c[2];              // the light sample's phi
+    if (!same_bits(1.0f - R, rng_one_minus(kf))) ++c[3];                // 1.0f - eps1
+    for (int j = 0; j < kRngCamX; ++j)                                  // (float)x + R
+        if (!same_bits(camx[j] + R, rng_offset(kf, camx[j]))) ++c[kRngForms + j];
+}
+LRT_HD void rng_form_span(uint32_t first, uint32_t end, unsigned long long* c) {
+    for (uint32_t k = first; k < end; ++k) rng_form_case(k, c);
+}
+__attribute__((target("fma"))) static void rng_form_span_fma(uint32_t first, uint32_t end, unsigned long long* c) {
+    rng_form_span(first, end, c);
+}
+__global__ __launch_bounds__(256) void rng_form_kernel(unsigned long long* out) {
+    unsigned long long c[kRngForms + kRngCamX] = {};
+    const uint32_t step = gridDim.x * blockDim.x;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < (1u << 24); k += step) rng_form_case(k, c);
+    for (int j = 0; j < kRngForms + kRngCamX; ++j)
+        if (c[j]) atomicAdd(&out[j], c[j]);
+}
+
 // lrt_scatter_eval's case i: Scatter (lrt_trace.h, parallel.cpp:78-196) of material ids[i]
 // for the ray rays[6i..] (through the Ray ctor) at the hit recs[7i..] under RNG state seeds[i].
 template <int kAcc>
@@ -595,6 +625,46 @@ int lrt_exact_div_sweep(int what, unsigned long long first, unsigned long long c
         for (int k = 0; k < 3; ++k) out[k] += part[4 * (size_t)t + k];
         out[3] = std::min(out[3], part[4 * (size_t)t + 3]);
     }
+    return LRT_OK;
+}
+
+
+int lrt_rng_form_sweep(int on_device, unsigned long long* out) {
+    constexpr int kN = kRngForms + kRngCamX;
+    if (!out) return fail(LRT_E_INVALID, "rng form sweep: null output");
+    for (int j = 0; j < kN; ++j) out[j] = 0;
+    out[kN] = 1ull << 24;
+    if (on_device) {
+        unsigned long long* d = nullptr;
+        LRT_HIP(hipMalloc(&d, kN * sizeof(unsigned long long)));
+        hipError_t e = hipMemset(d, 0, kN * sizeof(unsigned long long));
+        if (e == hipSuccess) {
+            rng_form_kernel<<<4096, 256>>>(d);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(out, d, kN * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (e != hipSuccess) return fail(LRT_E_HIP, std::string("rng form sweep: ") + hipGetErrorString(e));
+        return LRT_OK;
+    }
+    const bool fma = __builtin_cpu_supports("fma");
+    const unsigned nt = std::max(1u, std::min(std::thread::hardware_concurrency(), 16u));
+    std::vector<unsigned long long> part((size_t)kN * nt, 0);
+    std::vector<std::thread> th;
+    constexpr uint32_t kChunk = 1u << 16;
+    for (unsigned t = 0; t < nt; ++t) {
+        unsigned long long* c = &part[(size_t)kN * t];
+        th.emplace_back([=] {
+            for (uint32_t a = t * kChunk; a < (1u << 24); a += nt * kChunk) {
+                if (fma) rng_form_span_fma(a, a + kChunk, c);
+                else rng_form_span(a, a + kChunk, c);
+            }
+        });
+    }
+    for (auto& x : th) x.join();
+    for (unsigned t = 0; t < nt; ++t)
+        for (int j = 0; j < kN; ++j) out[j] += part[(size_t)kN * t + j];
     return LRT_OK;
 }
 

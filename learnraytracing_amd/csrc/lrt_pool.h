@@ -50,6 +50,39 @@ typedef const KernelArgs* KArgPtr;
 __device__ __forceinline__ KArgPtr opaque_args() { return nullptr; }
 #endif
 
+// c ? a : b by value, a select per component (on the structs a ?: picks an address)
+__device__ __forceinline__ F3 sel(bool c, F3 a, F3 b) { return f3(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z); }
+// Any value, at no instruction: for a variable's lanes (or paths) that never read it, so that the
+// join neither copies a default in nor sees an undefined input. (volatile: stays where it is.)
+__device__ __forceinline__ void any_value(float& x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "=v"(x));
+#else
+    x = 0.0f;
+#endif
+}
+__device__ __forceinline__ void any_value(int& x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "=v"(x));
+#else
+    x = 0;
+#endif
+}
+__device__ __forceinline__ void any_value(F3& v) { any_value(v.x), any_value(v.y), any_value(v.z); }
+
+// A lane predicate the optimiser cannot see through (an empty asm launders it): selects on it
+// stay selects. Left visible, the bounce loop's selects under `cont` were sunk into the branch
+// that guards the stack write under the same condition and came back as register copies.
+__device__ __forceinline__ bool opaque_pred(bool c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    int v = c ? 1 : 0;
+    asm volatile("" : "+v"(v));
+    return v != 0;
+#else
+    return c;
+#endif
+}
+
 // The grid's spheres tested first by every query (the ground, the light: GridStart) are read
 // from an LDS copy (at a.bvh_stack_offset: the grid has no traversal stack) instead of through
 // L1/L2, and their uniform loads leave the walk's latency chain.
@@ -348,80 +381,91 @@ __global__ __launch_bounds__(64 * kW, (pool_waves_per_eu<MAXD, kW, kNL, kChk>())
             dl.li = -1;
             dl.l = f3(0.0f, 0.0f, 0.0f);
             dl.contrib = f3(0.0f, 0.0f, 0.0f);
+            // The refill stage is a loop of its own (it repeats while no lane traces: a pool whose
+            // next samples all lie outside the window) so that the bounce pass below ends in the
+            // outer loop's only latch. As one loop with a `continue`, the two back edges shared a
+            // block, the carried state of both was live there in two register sets, and every
+            // bounce copied one into the other (22 v_mov_b32, profiles/r10_carry).
             for (;;) {
-                // ---- refill: ended paths are folded and their lanes take the pool's next
-                // samples, together once a.regenMin lanes wait (or no path is left to trace),
-                // so the fold and the camera rays run with more lanes than end per bounce ----
-                const unsigned long long waitM = __ballot(state == kPoolIdle || state == kPoolEnded);
-                if (waitM && (__popcll(waitM) >= a.regenMin || __ballot(state == kPoolTrace) == 0)) {
-                    if (state == kPoolEnded) {   // :214 folded leaf-outwards into the sample's slot
-                        sec_count(sc, kSecFold);
-                        F3 T = carry;
-                        for (int d = depth - 1; d >= 0; --d) {
-                            const float4 s = get(d);
-                            const float4 b = sc.mats[3 * __float_as_int(s.w) + 2];
-                            T = f3(s.x, s.y, s.z) + f3(b.x, b.y, b.z) * T;
+                unsigned long long traceM;
+                bool dry = false;
+                for (;;) {   // until a lane traces, or the pool is dry
+                    // ---- refill: ended paths are folded and their lanes take the pool's next
+                    // samples, together once a.regenMin lanes wait (or no path is left to trace),
+                    // so the fold and the camera rays run with more lanes than end per bounce ----
+                    const unsigned long long waitM = __ballot(state == kPoolIdle || state == kPoolEnded);
+                    if (waitM && (__popcll(waitM) >= a.regenMin || __ballot(state == kPoolTrace) == 0)) {
+                        if (state == kPoolEnded) {   // :214 folded leaf-outwards into the sample's slot
+                            sec_count(sc, kSecFold);
+                            F3 T = carry;
+                            for (int d = depth - 1; d >= 0; --d) {
+                                const float4 s = get(d);
+                                const float4 b = sc.mats[3 * __float_as_int(s.w) + 2];
+                                T = f3(s.x, s.y, s.z) + f3(b.x, b.y, b.z) * T;
+                            }
+                            slots[3 * k] = T.x;
+                            slots[3 * k + 1] = T.y;
+                            slots[3 * k + 2] = T.z;
+                            state = kPoolIdle;
                         }
-                        slots[3 * k] = T.x;
-                        slots[3 * k + 1] = T.y;
-                        slots[3 * k + 2] = T.z;
-                        state = kPoolIdle;
-                    }
-                    const unsigned long long needM = waitM;
-                    if (state == kPoolIdle) {
-                        // (slim: mbcnt counts the lanes below without the two registers of `below`)
-                        if constexpr (kSlim)
-                            k = next + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(needM >> 32),
-                                                                      __builtin_amdgcn_mbcnt_lo((unsigned)needM, 0u));
-                        else
-                            k = next + __popcll(needM & below);
-                        state = kPoolDone;
-                        if (k < N) {
-                            const int j = k & ((1 << lgP) - 1), f = fr0 + (k >> lgP);
-                            const int lx = tx0 + (j & ((1 << lgW) - 1)), ly = ty0 + (j >> lgW);
-                            // What a path start reads from the kernel arguments (window, row map,
-                            // camera: contiguous in KernelArgs), asked for in one batch of scalar
-                            // loads: one wait, where a read per dependent test made five. (Asked
-                            // ahead of the fold instead, the 30 scalars held across it cost the
-                            // general instances scratch and gained the trimmed one nothing,
-                            // profiles/r7_trim.)
-                            const KArgPtr pa = opaque_args();
-                            const int wx0 = pa->x0, wxc = pa->xc, wy0 = pa->y0, wrows = pa->rows;
-                            const int rb = pa->rb, rp = pa->rp, rph = pa->rph, rowIdent = pa->rowIdent;
-                            const CameraDev cam = pa->cam;
-                            if (lx < wxc && ly < wrows) {   // TraceRowJob's per-pixel body (:270-279)
-                                sec_count(sc, kSecCamera);
-                                const int x = wx0 + lx;
-                                // GlobalRow; an unsharded window's row map is the identity, and the
-                                // (wave-uniform) flag spares it the division
-                                int y = wy0 + ly;
-                                if (!rowIdent) y = wy0 + (ly / rb) * rb * rp + rph * rb + ly % rb;
-                                rng = PixelSeed((uint32_t)x, (uint32_t)y, (uint32_t)f);
-                                const float u = ((float)x + RandomFloat01(rng)) * invWidth;    // :272
-                                const float v = ((float)y + RandomFloat01(rng)) * invHeight;   // :273
-                                r = GetRay(cam, u, v, rng, sc.rnlut);
-                                depth = 0;
-                                prevLambert = false;
-                                pend = false;
-                                state = kPoolTrace;
-                            } else {
-                                state = kPoolIdle;   // outside the window: nothing to trace
+                        const unsigned long long needM = waitM;
+                        if (state == kPoolIdle) {
+                            // (slim: mbcnt counts the lanes below without the two registers of `below`)
+                            if constexpr (kSlim)
+                                k = next + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(needM >> 32),
+                                                                          __builtin_amdgcn_mbcnt_lo((unsigned)needM, 0u));
+                            else
+                                k = next + __popcll(needM & below);
+                            state = kPoolDone;
+                            if (k < N) {
+                                const int j = k & ((1 << lgP) - 1), f = fr0 + (k >> lgP);
+                                const int lx = tx0 + (j & ((1 << lgW) - 1)), ly = ty0 + (j >> lgW);
+                                // What a path start reads from the kernel arguments (window, row map,
+                                // camera: contiguous in KernelArgs), asked for in one batch of scalar
+                                // loads: one wait, where a read per dependent test made five. (Asked
+                                // ahead of the fold instead, the 30 scalars held across it cost the
+                                // general instances scratch and gained the trimmed one nothing,
+                                // profiles/r7_trim.)
+                                const KArgPtr pa = opaque_args();
+                                const int wx0 = pa->x0, wxc = pa->xc, wy0 = pa->y0, wrows = pa->rows;
+                                const int rb = pa->rb, rp = pa->rp, rph = pa->rph, rowIdent = pa->rowIdent;
+                                const CameraDev cam = pa->cam;
+                                if (lx < wxc && ly < wrows) {   // TraceRowJob's per-pixel body (:270-279)
+                                    sec_count(sc, kSecCamera);
+                                    const int x = wx0 + lx;
+                                    // GlobalRow; an unsharded window's row map is the identity, and the
+                                    // (wave-uniform) flag spares it the division
+                                    int y = wy0 + ly;
+                                    if (!rowIdent) y = wy0 + (ly / rb) * rb * rp + rph * rb + ly % rb;
+                                    rng = PixelSeed((uint32_t)x, (uint32_t)y, (uint32_t)f);
+                                    const float u = rng_offset(RandomK24(rng), (float)x) * invWidth;    // :272
+                                    const float v = rng_offset(RandomK24(rng), (float)y) * invHeight;   // :273
+                                    r = GetRay(cam, u, v, rng, sc.rnlut);
+                                    depth = 0;
+                                    prevLambert = false;
+                                    pend = false;
+                                    state = kPoolTrace;
+                                } else {
+                                    state = kPoolIdle;   // outside the window: nothing to trace
+                                }
+                            }
+                        }
+                        next += __popcll(needM);
+                        if constexpr (kLate) {
+                            if (!asked && next >= N && fr0 + roundFrames >= fend) {   // the tile's last samples
+                                if (lane == 0) fetched = atomicAdd(ctr, 1ull);
+                                asked = true;
                             }
                         }
                     }
-                    next += __popcll(needM);
-                    if constexpr (kLate) {
-                        if (!asked && next >= N && fr0 + roundFrames >= fend) {   // the tile's last samples
-                            if (lane == 0) fetched = atomicAdd(ctr, 1ull);
-                            asked = true;
-                        }
+                    traceM = __ballot(state == kPoolTrace);
+                    if (traceM != 0) break;
+                    if (__ballot(state == kPoolIdle || state == kPoolEnded) == 0) {   // the pool is dry
+                        dry = true;
+                        break;
                     }
                 }
-                const unsigned long long traceM = __ballot(state == kPoolTrace);
-                if (traceM == 0) {
-                    if (__ballot(state == kPoolIdle || state == kPoolEnded) == 0) break;   // the pool is dry
-                    continue;
-                }
+                if (dry) break;
                 // A wave tracing few paths (its pool draining) yields the SIMD's issue slots to the
                 // fuller waves beside it: config 2 alone 0.2598 -> 0.2527 ms, two streams and
                 // configs 3-4 within noise (profiles/r5_al); the depth-8 one-wave instances only
@@ -434,21 +478,29 @@ __global__ __launch_bounds__(64 * kW, (pool_waves_per_eu<MAXD, kW, kNL, kChk>())
                 constexpr bool coherent = false;
                 sec_enter(sc, kSecOther, false);
                 // ---- one bounce of every traced path: Trace's body (parallel.cpp:202-226) ----
-                int nid = -1;
-                float nt = 0.0f;
-                bool shade = false, fin = false;
-                F3 leaf = f3(0.0f, 0.0f, 0.0f);
-                if (state == kPoolTrace) {
+                // The loop-carried path state (r, dl, carry, pend, prevLambert, depth, idw, state)
+                // is read by the hit pass and the material code and WRITTEN ONCE, at the bottom,
+                // each value under one predicate: the material code leaves the next ray, the stack
+                // entry and the deferred light in temporaries. Written inside the nested guards
+                // instead, every value took a register copy at each of their joins and at the
+                // latch (83 v_mov_b32 per iteration at full wave width, profiles/r10_carry).
+                const bool tr = state == kPoolTrace;
+                // the hit pass's results: set by the lanes that trace, read by them alone
+                // (no default: a default would be copied in for the lanes that do not trace)
+                int nid;
+                float nt;
+                bool lit;
+                if (tr) {
                     // HitWorld of r (:204-205) and the pending shadow ray (:122-123) in one pass
                     sec_count(sc, coherent ? kSecHit0 : kSecHit);
-                    ++rays;
-                    bool lit = false;
                     const bool hasS = pend && dl.on;
                     if constexpr (kAcc == kAccGrid) {
                         const float4 ls = hasS ? sc.sph[dl.li] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                         const GridView gv = pool_grid_view<kAcc, kW>(smem);
+                        lit = false;
                         nid = ClosestHitDualGrid<(kW > 1 ? 1 : 0)>(r.orig, r.dir, hasS, dl.l, dl.li, ls, gv, nt, lit);
                     } else if constexpr (kAcc == kAccBvh) {
+                        lit = false;
                         if (coherent) {
                             nid = ClosestHitBVH(r.orig, r.dir, sc.bv, nt, sc.bstk, sc.bstride, nullptr, true);
                         } else {
@@ -461,19 +513,36 @@ __global__ __launch_bounds__(64 * kW, (pool_waves_per_eu<MAXD, kW, kNL, kChk>())
                         DualClosestHit<kNS, kChk>(r.orig, r.dir, hasS, dl.l, sc, nid, nt, sid);
                         lit = hasS && sid == dl.li;
                     }
-                    if (pend) {   // the scatter event that produced r (:214), with its light if reached
-                        if (lit) put(depth, make_float4(carry.x, carry.y, carry.z, __int_as_float(dl.id)));
-                        ++depth;
-                        pend = false;
-                    }
-                    if (nid < 0) {   // sky (:223-225)
-                        const float t = 0.5f * (r.dir.y + 1.0f);
-                        leaf = ((1.0f - t) * f3(1.0f, 1.0f, 1.0f) + t * f3(0.5f, 0.7f, 1.0f)) * 0.3f;
-                        fin = true;
+                } else {
+                    any_value(nid), any_value(nt);
+                    lit = false;
+                }
+                rays += tr ? 1 : 0;
+                // the scatter event that produced r (:214) now counts; with its light if reached:
+                // its stack entry (this level's, written when the event was found) takes carry.
+                // The entry's material id is the one already there (dl.id).
+                const bool was = tr && pend;
+                if (was && lit) {
+                    if constexpr (kSlim) {
+                        pstk[depth * 64] = carry.x;
+                        pstk[(kLv + depth) * 64] = carry.y;
+                        pstk[(2 * kLv + depth) * 64] = carry.z;
                     } else {
-                        shade = true;
+                        put(depth, make_float4(carry.x, carry.y, carry.z, __int_as_float(dl.id)));
                     }
                 }
+                const int lvl = depth + (was ? 1 : 0);   // the level a scatter event found now would take
+                const bool shade = tr && nid >= 0;
+                // what the material code leaves for the bottom: cont = the path goes on from a new
+                // scatter event (shade && lvl < maxDepth && not absorbed); its ray, stack entry e,
+                // carry-to-be cv, deferred light nd; leaf = the colour of a path that ends here
+                bool cont = false;
+                // (set where cont, or for leaf where the path ends, and read under those alone)
+                F3 leaf, npos, ndir, e, cv;
+                DeferredLight nd;
+                nd.on = false;
+                nd.contrib = f3(0.0f, 0.0f, 0.0f);
+                int nLamb;
                 if (shade) {   // HitWorld's winner (maths.cpp:74-76,86-88), then Scatter (:210-212)
                     const float4 sp4 = sc.sph[nid];
                     Hit rec;
@@ -482,33 +551,65 @@ __global__ __launch_bounds__(64 * kW, (pool_waves_per_eu<MAXD, kW, kNL, kChk>())
                     rec.t = nt;
                     const Material mat = load_material(sc.mats, nid);
                     F3 matE = mat.emissive;
-                    fin = true;
                     leaf = matE;
-                    if (depth < a.maxDepth) {
+                    if (lvl < a.maxDepth) {
                         F3 lightE;
-                        dl.on = false;
+                        any_value(nd.l), any_value(nd.li);   // (a scatter without a deferred light sets neither)
                         if constexpr (kAcc == kAccGrid) sc.gv = pool_grid_view<kAcc, kW>(smem);   // other lights' shadow rays
-                        const F3 X = ScatterDir<kAcc, kNS, kNL>(mat, nid, r, rec, lightE, rays, rng, sc, &dl, coherent);
+                        const F3 X = ScatterDir<kAcc, kNS, kNL>(mat, nid, r, rec, lightE, rays, rng, sc, &nd, coherent);
                         sec_count(sc, kSecPost);
-                        const F3 dir = renormalize(normalize(X), sc.rnlut);   // Ray(rec.pos, normalize(X))
-                        if ((mat.type != 1) | (dot(dir, rec.normal) > 0.0f)) {    // Metal absorbs (:147)
-                            if (a.ndl && prevLambert) matE = f3(0.0f, 0.0f, 0.0f);
-                            prevLambert = mat.type == 0;
-                            const F3 e = matE + lightE;
-                            put(depth, make_float4(e.x, e.y, e.z, __int_as_float(nid)));
-                            if (dl.on) carry = matE + (lightE + dl.contrib);   // TraceDual's order
-                            dl.id = nid;
-                            pend = true;
-                            r.orig = rec.pos;
-                            r.dir = dir;
-                            fin = false;
-                        }
+                        ndir = renormalize(normalize(X), sc.rnlut);   // Ray(rec.pos, normalize(X))
+                        npos = rec.pos;
+                        cont = (mat.type != 1) | (dot(ndir, rec.normal) > 0.0f);    // Metal absorbs (:147)
+                        if (a.ndl && prevLambert) matE = f3(0.0f, 0.0f, 0.0f);
+                        nLamb = mat.type == 0 ? 1 : 0;
+                        e = matE + lightE;
+                        cv = matE + (lightE + nd.contrib);   // TraceDual's order (read only where nd.on)
+                    } else {
+                        any_value(npos), any_value(ndir), any_value(e), any_value(cv), any_value(nd.l);
+                        any_value(nd.li), any_value(nLamb);
+                    }
+                } else {
+                    if (tr) {   // sky (:223-225)
+                        const float t = 0.5f * (r.dir.y + 1.0f);
+                        leaf = ((1.0f - t) * f3(1.0f, 1.0f, 1.0f) + t * f3(0.5f, 0.7f, 1.0f)) * 0.3f;
+                    } else {
+                        any_value(leaf);
+                    }
+                    any_value(npos), any_value(ndir), any_value(e), any_value(cv), any_value(nd.l);
+                    any_value(nd.li), any_value(nLamb);
+                }
+                // ---- the carried state's one write each ----
+                const bool contS = opaque_pred(cont);
+                if (cont) {   // the new event's stack entry; it counts (depth) once its ray is traced
+                    if constexpr (kSlim) {
+                        pstk[lvl * 64] = e.x;
+                        pstk[(kLv + lvl) * 64] = e.y;
+                        pstk[(2 * kLv + lvl) * 64] = e.z;
+                    } else {
+                        put(lvl, make_float4(e.x, e.y, e.z, __int_as_float(nid)));
                     }
                 }
-                if (fin) {   // the path's leaf colour waits for the fold at the next refill
-                    carry = leaf;
-                    state = kPoolEnded;
+                if constexpr (kSlim) {
+                    const int sh = 4 * (lvl & 7);   // (lvl = 8 where the depth budget is spent: not cont)
+                    idw = contS ? (idw & ~(15u << sh)) | ((unsigned)nid << sh) : idw;
                 }
+                depth = lvl;
+                pend = contS;   // (a lane that does not trace has nothing pending)
+                // The ray, the deferred light and prevLambert are read by the lanes that trace the
+                // next iteration alone, and those either continue here (cont) or take a new path at
+                // the refill, which sets them: the other lanes may hold anything, so no select.
+                prevLambert = nLamb != 0;
+                r.orig = npos;
+                r.dir = ndir;
+                dl.l = nd.l;
+                dl.li = nd.li;
+                dl.on = nd.on;
+                if constexpr (!kSlim) dl.id = nid;
+                // the path's leaf colour waits for the fold at the next refill; a lane that does
+                // not trace keeps its own (an ended path's, until it is folded)
+                carry = sel(tr, sel(contS, cv, leaf), carry);
+                state = (tr && !contS) ? (int)kPoolEnded : state;
             }
             // ---- the round's colours in frame order, one lane per pixel (:262,282) ---------
             // Lane j owns pixels j, j + 64, ... of the tile. Its address and previous value are

@@ -41,8 +41,8 @@ __global__ __launch_bounds__(64) void probe_kernel(const KernelArgs a, unsigned*
     if (tile < ntiles && lx < a.xc && ly < a.rows) {
         const int x = a.x0 + lx, y = GlobalRow(a, ly);
         uint32_t rng = PixelSeed((uint32_t)x, (uint32_t)y, (uint32_t)a.frame0);
-        const float u = ((float)x + RandomFloat01(rng)) * (1.0f / (float)a.width);
-        const float v = ((float)y + RandomFloat01(rng)) * (1.0f / (float)a.height);
+        const float u = rng_offset(RandomK24(rng), (float)x) * (1.0f / (float)a.width);
+        const float v = rng_offset(RandomK24(rng), (float)y) * (1.0f / (float)a.height);
         const Ray r = GetRay(a.cam, u, v, rng, nullptr);
         float t;
         const int id = ClosestHitSV<kAcc, 0>(r, kMinT, kMaxT, sc, t);

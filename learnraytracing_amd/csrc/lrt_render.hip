@@ -238,7 +238,9 @@ int pool_tiles(int pix, int xc, int rows) {
     const int tx = pix >= 128 ? 16 : pix >= 32 ? 8 : pix >= 8 ? 4 : pix >= 2 ? 2 : 1, ty = pix / tx;
     return ((xc + tx - 1) / tx) * ((rows + ty - 1) / ty);
 }
+static int g_pool_force_pix = 0;   // lrt_pool_force_pix (tests): the tile size whatever the policy says
 int pool_pixels(int frames, int xc, int rows, int cap) {
+    if (g_pool_force_pix && g_pool_force_pix * frames <= kPoolSamples) return g_pool_force_pix;
     const long long slots = 16LL * ctx().num_cus;   // resident waves (4 per SIMD)
     for (int pix : {256, 128, 64, 32, 16})
         if (cap >= pix && pix * frames <= kPoolSamples && (pix <= 64 || pool_tiles(pix, xc, rows) >= slots))
@@ -496,3 +498,10 @@ int auto_kernel(const KernelArgs& a, const lrt_render_desc* d, bool feat, int pi
 }
 
 }  // namespace lrt
+
+extern "C" int lrt_pool_force_pix(int pix) {
+    if (pix != 0 && pix != 16 && pix != 32 && pix != 64 && pix != 128 && pix != 256)
+        return lrt::fail(LRT_E_INVALID, "lrt_pool_force_pix: 0, 16, 32, 64, 128 or 256");
+    lrt::g_pool_force_pix = pix;
+    return LRT_OK;
+}

@@ -251,18 +251,35 @@ LRT_DEV uint32_t XorShift32(uint32_t& s) {
     return x;
 }
 LRT_DEV float RandomFloat01(uint32_t& s) { return (float)(XorShift32(s) & 0xFFFFFF) * (1.0f / 16777216.0f); }
+// The draw's integer k = XorShift32 & 0xFFFFFF as a float, kf: exact (k < 2^24), and so is every
+// product of kf with a power of two. Where a draw R = kf * 2^-24 only enters a sum or a product
+// whose other steps are exact, the source's chain has ONE rounding, and the forms below take that
+// rounding in one instruction (explicit fma: the build has contraction off). Each returns the bits
+// of the source form for every k (swept on the host and on gfx950, lrt_rng_form_sweep):
+//  * 2 R - 1 (the rejection candidates, RandomUnitVector's z): 2 R = kf * 2^-23 is exact, so the
+//    source rounds kf * 2^-23 - 1 once, as fma(kf, 2^-23, -1) does.
+//  * R * 2 * kPI and 2 * kPI * R: R * 2 and 2 * kPI are exact, so each is one rounding of the
+//    real product kf * 2^-23 * kPI, as kf * (kPI * 2^-23) is (the constant is kPI's significand,
+//    exact; the smallest non-zero product, 3.7e-7, is far above the denormals).
+//  * (float)x + R (the camera's pixel offset) and 1 - R: one rounding of x + kf * 2^-24 and of
+//    1 - kf * 2^-24.
+LRT_DEV float RandomK24(uint32_t& s) { return (float)(XorShift32(s) & 0xFFFFFF); }
+LRT_DEV float rng_signed(float kf) { return __builtin_fmaf(kf, 0x1p-23f, -1.0f); }            // 2 R - 1
+LRT_DEV float rng_angle(float kf) { return kf * (kPI * 0x1p-23f); }                           // R * 2 * kPI
+LRT_DEV float rng_offset(float kf, float x) { return __builtin_fmaf(kf, 0x1p-24f, x); }       // x + R
+LRT_DEV float rng_one_minus(float kf) { return __builtin_fmaf(kf, -0x1p-24f, 1.0f); }         // 1 - R
 LRT_DEV F3 RandomInUnitDisk(uint32_t& s) {
     F3 p;
     do {
-        float a = RandomFloat01(s);
-        float b = RandomFloat01(s);
-        p = 2.0f * f3(a, b, 0.0f) - f3(1.0f, 1.0f, 0.0f);
+        float a = RandomK24(s);
+        float b = RandomK24(s);
+        p = f3(rng_signed(a), rng_signed(b), 0.0f);   // 2.0f * f3(a, b, 0) - f3(1, 1, 0)
     } while (dot(p, p) >= 1.0f);
     return p;
 }
 LRT_DEV F3 RandomUnitVector(uint32_t& s) {
-    float z = RandomFloat01(s) * 2.0f - 1.0f;
-    float a = RandomFloat01(s) * 2.0f * kPI;
+    float z = rng_signed(RandomK24(s));   // RandomFloat01() * 2.0f - 1.0f
+    float a = rng_angle(RandomK24(s));    // RandomFloat01() * 2.0f * kPI
     float r = sqrt_rn(1.0f - z * z);
     float sa, ca;
     libm::sincosf(a, &sa, &ca);   // bit-identical to separate cosf(a), sinf(a)
@@ -273,10 +290,10 @@ LRT_DEV F3 RandomUnitVector(uint32_t& s) {
 LRT_DEV F3 RandomInUnitSphere(uint32_t& s) {
     F3 p;
     do {
-        float a = RandomFloat01(s);
-        float b = RandomFloat01(s);
-        float c = RandomFloat01(s);
-        p = 2.0f * f3(a, b, c) - f3(1.0f, 1.0f, 1.0f);
+        float a = RandomK24(s);
+        float b = RandomK24(s);
+        float c = RandomK24(s);
+        p = f3(rng_signed(a), rng_signed(b), rng_signed(c));   // 2.0f * f3(a, b, c) - f3(1, 1, 1)
         // the reference tests p.length() >= 1.0 (maths.cpp:47). With s = x*x + y*y + z*z
         // summed in the same order, the correctly rounded sqrt(s) >= 1 iff s >= 1:
         // sqrt(1 - 2^-24) = 1 - 2^-25 - 2^-51 rounds down to 1 - 2^-24, and sqrt is
@@ -523,11 +540,11 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
             F3 su = normalize(cross(__builtin_fabsf(sw.x) > 0.01f ? f3(0.0f, 1.0f, 0.0f) : f3(1.0f, 0.0f, 0.0f), sw));
             F3 sv = cross(sw, su);
             float cosAMax = sqrt_rn(1.0f - s.w / (len * len));                    // :109
-            float eps1 = RandomFloat01(rng);
-            float eps2 = RandomFloat01(rng);
-            float cosA = 1.0f - eps1 + eps1 * cosAMax;
+            const float k1 = RandomK24(rng);
+            float eps1 = k1 * (1.0f / 16777216.0f);   // RandomFloat01
+            float cosA = rng_one_minus(k1) + eps1 * cosAMax;   // 1.0f - eps1 + eps1 * cosAMax
             float sinA = sqrt_rn(1.0f - cosA * cosA);
-            float phi = 2.0f * kPI * eps2;
+            float phi = rng_angle(RandomK24(rng));   // 2.0f * kPI * eps2
             float sphi, cphi;
             libm::sincosf(phi, &sphi, &cphi);   // bit-identical to cosf(phi), sinf(phi)
             F3 l = su * cphi * sinA + sv * sphi * sinA + sw * cosA;                         // :116

@@ -164,8 +164,8 @@ __global__ __launch_bounds__(kBlock, kWavesPerEU) void trace_kernel(const Kernel
             if (valid && f < fend) {
                 uint32_t rng = PixelSeed((uint32_t)x, (uint32_t)y, (uint32_t)f);
                 sec_count(sc, kSecCamera);
-                float u = ((float)x + RandomFloat01(rng)) * invWidth;              // :272
-                float v = ((float)y + RandomFloat01(rng)) * invHeight;             // :273
+                float u = rng_offset(RandomK24(rng), (float)x) * invWidth;              // :272
+                float v = rng_offset(RandomK24(rng), (float)y) * invHeight;             // :273
                 Ray r = GetRay(a.cam, u, v, rng, sc.rnlut);
                 col = Trace<MAXD, kAcc, kFeat, kTraceLdsLevels, kNS>(r, a.maxDepth, rays, rng, sc, smem + tid, kBlock, a.ovf + gtid,
                                                gthreads, a.ndl, feat);

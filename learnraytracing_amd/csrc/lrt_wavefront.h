@@ -151,8 +151,8 @@ __global__ __launch_bounds__(kWfBlock) void wf_camera(const WfArgs w) {
         const int x = a.x0 + lx;
         const int y = a.y0 + (ly / a.rb) * a.rb * a.rp + a.rph * a.rb + ly % a.rb;
         uint32_t rng = PixelSeed((uint32_t)x, (uint32_t)y, (uint32_t)f);
-        const float u = ((float)x + RandomFloat01(rng)) * invWidth;   // :272
-        const float v = ((float)y + RandomFloat01(rng)) * invHeight;  // :273
+        const float u = rng_offset(RandomK24(rng), (float)x) * invWidth;   // :272
+        const float v = rng_offset(RandomK24(rng), (float)y) * invHeight;  // :273
         const Ray r = GetRay(a.cam, u, v, rng, s_lut);
         const size_t slot = (size_t)j * w.R0 + k;
         w.rng[slot] = rng;
