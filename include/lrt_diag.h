@@ -47,6 +47,13 @@ int lrt_exact_div_sweep(int what, unsigned long long first, unsigned long long c
  * where the CPU has it, several threads); otherwise one launch on the current device. Blocking. */
 int lrt_rng_form_sweep(int on_device, unsigned long long* out);
 
+/* The closest-hit scan's root selection (lrt_trace.h: SphereRoots, the checked form) on given
+ * operands (host only, no GPU): case i starts from closestT[i] with no sphere found and tests one
+ * sphere with rsProj[i], ifHit[i] against tMin[i]. t_out[i]: closestT after; hit_out[i]: 1 where the
+ * sphere was taken. The test compares them with the source's if / else-if (maths.cpp:61-90). */
+int lrt_sphere_roots_eval(const float* rsProj, const float* ifHit, const float* tMin, const float* closestT, int n,
+                          float* t_out, int* hit_out);
+
 /* BVH diagnostics (host only, no GPU): build the BVH of the given scene and trace n rays
  * (6 floats each: origin, direction) with the device traversal code. out[7]: mean nodes
  * visited, mean spheres tested, max nodes, max spheres, mismatches per ray against the

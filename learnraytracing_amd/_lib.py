@@ -330,6 +330,7 @@ DIAG_SIGNATURES = {
     "lrt_libm_eval_device": (_i, [_i, _vp, _vp, _c.c_longlong]),
     "lrt_exact_div_sweep": (_i, [_i, _c.c_ulonglong, _c.c_ulonglong, _i, _vp]),
     "lrt_rng_form_sweep": (_i, [_i, _vp]),
+    "lrt_sphere_roots_eval": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "lrt_pool_force_pix": (_i, [_i]),
     "lrt_bvh_stats": (_i, [_c.POINTER(Sphere), _i, _vp, _i, _vp]),
     "lrt_grid_stats": (_i, [_c.POINTER(Sphere), _i, _vp, _i, _vp]),

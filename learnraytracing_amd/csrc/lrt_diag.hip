@@ -669,6 +669,21 @@ int lrt_rng_form_sweep(int on_device, unsigned long long* out) {
 }
 
 
+int lrt_sphere_roots_eval(const float* rsProj, const float* ifHit, const float* tMin, const float* closestT, int n,
+                          float* t_out, int* hit_out) {
+    if (!rsProj || !ifHit || !tMin || !closestT || !t_out || !hit_out || n < 0)
+        return fail(LRT_E_INVALID, "sphere roots eval: invalid arguments");
+    for (int i = 0; i < n; ++i) {
+        float t = closestT[i];
+        int id = -1;
+        SphereRoots<true>(rsProj[i], ifHit[i], tMin[i], t, id, 0);
+        t_out[i] = t;
+        hit_out[i] = id == 0 ? 1 : 0;
+    }
+    return LRT_OK;
+}
+
+
 // ---- kernel timing (lrt_kernel_timing) ----------------------------------------------------
 int lrt_kernel_timing(int on) {
     lrt::g_ktiming_on = on != 0;

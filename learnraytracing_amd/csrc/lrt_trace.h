@@ -23,6 +23,18 @@ constexpr float kPI = 3.1415926f;     // maths.h:5
 constexpr float kMinT = 0.001f;       // parallel.cpp:9
 constexpr float kMaxT = 1.0e7f;       // parallel.cpp:10
 
+// A/B builds only (profiles/r11_shade prices each with a build that has it alone taken out); the
+// defaults are the kept state, and every setting gives the same bits.
+#ifndef LRT_SHADE_HEAD
+#define LRT_SHADE_HEAD 1    // ScatterDir: dot(r_in.dir, rec.normal) and reflect once for the three materials
+#endif
+#ifndef LRT_SHADE_DRAWS
+#define LRT_SHADE_DRAWS 1   // ScatterDir: the scatter's first three draws taken once
+#endif
+#ifndef LRT_SHADE_ROOT1
+#define LRT_SHADE_ROOT1 1   // SphereRoots: one root chosen first
+#endif
+
 struct float3_ { float x, y, z; };    // maths.h:10-61 (own type: no vendor operators)
 using F3 = float3_;
 
@@ -199,7 +211,18 @@ LRT_DEV F3 member_quot(F3 v, float l) {
 // l = su cos sin + sv sin sin + sw cos, has length 1 to a few ulps, so the range test is
 // essentially never failed.
 LRT_DEV F3 normalize_member(F3 v) { return member_quot(v, length(v)); }
+// reflect and refract with their dot(v, n) handed in (ScatterDir computes it once for the three
+// materials): every other operation, and its order, is the source's.
+LRT_DEV F3 reflect_dn(F3 v, F3 n, float dn) { return v + 2.0f * (-dn * n); }
 LRT_DEV F3 reflect(F3 v, F3 n) { return v + 2.0f * (-dot(v, n) * n); }             // maths.h:100-103
+LRT_DEV bool refract_dt(F3 v, F3 n, float dt, float nint, F3& out) {
+    float discr = 1.0f - nint * nint * (1.0f - dt * dt);
+    if (discr > 0) {
+        out = nint * (v - n * dt) - n * sqrt_rn(discr);
+        return true;
+    }
+    return false;
+}
 LRT_DEV bool refract(F3 v, F3 n, float nint, F3& out) {                             // maths.h:106-118
     float dt = dot(v, n);
     float discr = 1.0f - nint * nint * (1.0f - dt * dt);
@@ -277,6 +300,19 @@ LRT_DEV F3 RandomInUnitDisk(uint32_t& s) {
     } while (dot(p, p) >= 1.0f);
     return p;
 }
+// RandomUnitVector and RandomInUnitSphere from draws already taken (kz, ka; a, b, c: RandomK24's
+// floats, in stream order). ScatterDir takes a scatter's first three draws once for whichever
+// materials the wave's lanes hold; the functions of the source's names take their own draws.
+LRT_DEV F3 UnitVectorOf(float kz, float ka) {
+    float z = rng_signed(kz);   // RandomFloat01() * 2.0f - 1.0f
+    float a = rng_angle(ka);    // RandomFloat01() * 2.0f * kPI
+    float r = sqrt_rn(1.0f - z * z);
+    float sa, ca;
+    libm::sincosf(a, &sa, &ca);   // bit-identical to separate cosf(a), sinf(a)
+    float x = r * ca;
+    float y = r * sa;
+    return f3(x, y, z);
+}
 LRT_DEV F3 RandomUnitVector(uint32_t& s) {
     float z = rng_signed(RandomK24(s));   // RandomFloat01() * 2.0f - 1.0f
     float a = rng_angle(RandomK24(s));    // RandomFloat01() * 2.0f * kPI
@@ -287,17 +323,29 @@ LRT_DEV F3 RandomUnitVector(uint32_t& s) {
     float y = r * sa;
     return f3(x, y, z);
 }
+// (a, b, c): the first candidate's draws; s: the state after them, from which the retries go on
+LRT_DEV F3 InUnitSphereOf(float a, float b, float c, uint32_t& s) {
+    F3 p;
+    for (;;) {
+        p = f3(rng_signed(a), rng_signed(b), rng_signed(c));   // 2.0f * f3(a, b, c) - f3(1, 1, 1)
+        // the reference tests p.length() >= 1.0 (maths.cpp:47). With s = x*x + y*y + z*z
+        // summed in the same order, the correctly rounded sqrt(s) >= 1 iff s >= 1:
+        // sqrt(1 - 2^-24) = 1 - 2^-25 - 2^-51 rounds down to 1 - 2^-24, and sqrt is
+        // monotonic, so the sqrt can go
+        if (!(p.x * p.x + p.y * p.y + p.z * p.z >= 1.0f)) break;
+        a = RandomK24(s);
+        b = RandomK24(s);
+        c = RandomK24(s);
+    }
+    return p;
+}
 LRT_DEV F3 RandomInUnitSphere(uint32_t& s) {
     F3 p;
     do {
         float a = RandomK24(s);
         float b = RandomK24(s);
         float c = RandomK24(s);
-        p = f3(rng_signed(a), rng_signed(b), rng_signed(c));   // 2.0f * f3(a, b, c) - f3(1, 1, 1)
-        // the reference tests p.length() >= 1.0 (maths.cpp:47). With s = x*x + y*y + z*z
-        // summed in the same order, the correctly rounded sqrt(s) >= 1 iff s >= 1:
-        // sqrt(1 - 2^-24) = 1 - 2^-25 - 2^-51 rounds down to 1 - 2^-24, and sqrt is
-        // monotonic, so the sqrt can go
+        p = f3(rng_signed(a), rng_signed(b), rng_signed(c));   // as InUnitSphereOf
     } while (p.x * p.x + p.y * p.y + p.z * p.z >= 1.0f);
     return p;
 }
@@ -412,10 +460,30 @@ LRT_DEV void SphereRoots(float rsProj, float ifHit, float tMin, float& closestT,
     if (ifHit < 0.0f) {
         const float halfCut = kChk ? sqrt_rn(-ifHit) : sqrt_fast(-ifHit);
         const float t1 = rsProj - halfCut, t2 = rsProj + halfCut;
+#if LRT_SHADE_ROOT1
+        // One root chosen first: u = t1 > tMin ? t1 : t2, accepted iff t2 > tMin and u < closestT.
+        // Three compares and three selects for the source's four and three. halfCut >= 0 (a root,
+        // or +inf), so for a finite rsProj t2 = fl(p + h) >= fl(p - h) = t1: rounding is monotonic.
+        //  * t1 > tMin: then t2 >= t1 > tMin holds too, u = t1, and the test is t1 < closestT, the
+        //    source's first branch. Where it fails, t2 >= t1 >= closestT fails the second as well.
+        //  * otherwise (t1 <= tMin, or t1 NaN): the first branch is not taken, u = t2, and the test
+        //    is the second branch's, t2 > tMin && t2 < closestT.
+        // Operands that are not finite: a NaN rsProj makes ifHit NaN and never gets here; rsProj =
+        // +-inf makes ifHit -inf (or NaN), halfCut +inf, and one root NaN, the other +-inf: (NaN,
+        // +inf) gives u = +inf, not below closestT; (-inf, NaN) gives u = NaN and fails t2 > tMin;
+        // a finite rsProj with halfCut = +inf gives (-inf, +inf), u = +inf. The source accepts none
+        // of these either, and a NaN closestT or tMin fails every compare in both forms. Checked on
+        // the host over designed and random operands (lrt_sphere_roots_eval). DESIGN §2.
+        const float u = t1 > tMin ? t1 : t2;
+        const bool ok = (t2 > tMin) & (u < closestT);
+        id = ok ? i : id;
+        closestT = ok ? u : closestT;
+#else
         const bool ok1 = (t1 > tMin) & (t1 < closestT);
         const bool ok2 = (t2 > tMin) & (t2 < closestT);
         id = (ok1 | ok2) ? i : id;
         closestT = ok1 ? t1 : ok2 ? t2 : closestT;
+#endif
     }
 }
 
@@ -516,6 +584,40 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
                       int& inoutRayCount, uint32_t& rng, const SceneView& sc, DeferredLight* defer = nullptr,
                       bool coherent = false) {
     outLightE = f3(0.0f, 0.0f, 0.0f);
+    // The three materials' branches run one after the other for the lanes that hold each, and
+    // every instruction of a branch is issued whatever its lane count. What they share is issued
+    // once here, for every lane that scatters:
+    //  * dn = dot(r_in.dir, rec.normal). Metal's and Dielectric's reflect (maths.h:101) and
+    //    Dielectric's side test and cosine (:163-172) take it in this operand order. Lambert's nl
+    //    (:128) has dot(rec.normal, r_in.dir): each product has its operands commuted, which does
+    //    not change a product's bits, and the three are summed in the same order. Dielectric's
+    //    refract (maths.h:108) takes dot(rdir, outwardN) with outwardN = -rec.normal where dn > 0,
+    //    else rec.normal: in the first case every product is the exact negation of dn's, a sum of
+    //    negations is the negation of the sum under round-to-nearest unless the sum is zero (both
+    //    are +0 then, and the third product added to either gives the same), and the final sum,
+    //    -dn, is not zero; so dt = dn > 0 ? -dn : dn. Nothing is reassociated.
+    //  * the scatter's first three draws k1, k2, k3 with the states s1, s2, s3 after each. Lambert
+    //    consumes k1, k2 (RandomUnitVector) and, in the one-light instance, k3 as its light sample's
+    //    eps1 where that sample is taken (a Lambert that is itself the light leaves s2); Metal's
+    //    first candidate is (k1, k2, k3) and its retries go on from s3; Dielectric's decision is k1
+    //    and leaves s1. Each branch writes back the state the source's draw count leaves.
+    // The scan instances only: the BVH and grid instances walk their structure from in here with
+    // every register taken, and keep each branch's own code (any reshaping moved their spills).
+    constexpr bool kHead = LRT_SHADE_HEAD && kAcc == kAccScan;
+    constexpr bool kDraws = LRT_SHADE_DRAWS && kAcc == kAccScan;
+    // the one-light instance's single sample is the stream's third draw whenever it is taken
+    constexpr bool kShareK3 = kDraws && kNL == 1;
+    float dn = 0.0f;
+    if constexpr (kHead) dn = dot(r_in.dir, rec.normal);
+    uint32_t s1 = rng, s2 = rng, s3 = rng;
+    float k1 = 0.0f, k2 = 0.0f, k3 = 0.0f;
+    if constexpr (kDraws) {
+        k1 = RandomK24(s1);
+        s2 = s1;
+        k2 = RandomK24(s2);
+        s3 = s2;
+        k3 = RandomK24(s3);
+    }
     if (mat.type == 0) {  // Lambert :81-136
         sec_count(sc, kSecLambert);
         // the first light's index and sphere, read before RandomUnitVector: their two dependent
@@ -524,7 +626,17 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
         const int nlights = kNL > 0 ? kNL : sc.nlights;
         const int i0 = nlights > 0 ? sc.lights[0] : 0;
         const float4 s0 = sc.sph[i0];
-        F3 target = rec.pos + rec.normal + RandomUnitVector(rng);
+        F3 target;
+        if constexpr (kDraws) {
+            target = rec.pos + rec.normal + UnitVectorOf(k1, k2);
+            rng = s2;
+        } else {
+            target = rec.pos + rec.normal + RandomUnitVector(rng);
+        }
+        auto dnl = [&]() {   // nl's dot (:128)
+            if constexpr (kHead) return dn;
+            else return dot(rec.normal, r_in.dir);
+        };
         const F3 X = target - rec.pos;
         for (int k = 0; k < nlights; ++k) {
             int i = k == 0 ? i0 : sc.lights[k];
@@ -540,9 +652,15 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
             F3 su = normalize(cross(__builtin_fabsf(sw.x) > 0.01f ? f3(0.0f, 1.0f, 0.0f) : f3(1.0f, 0.0f, 0.0f), sw));
             F3 sv = cross(sw, su);
             float cosAMax = sqrt_rn(1.0f - s.w / (len * len));                    // :109
-            const float k1 = RandomK24(rng);
-            float eps1 = k1 * (1.0f / 16777216.0f);   // RandomFloat01
-            float cosA = rng_one_minus(k1) + eps1 * cosAMax;   // 1.0f - eps1 + eps1 * cosAMax
+            float ke;
+            if constexpr (kShareK3) {
+                ke = k3;
+                rng = s3;
+            } else {
+                ke = RandomK24(rng);
+            }
+            float eps1 = ke * (1.0f / 16777216.0f);   // RandomFloat01
+            float cosA = rng_one_minus(ke) + eps1 * cosAMax;   // 1.0f - eps1 + eps1 * cosAMax
             float sinA = sqrt_rn(1.0f - cosA * cosA);
             float phi = rng_angle(RandomK24(rng));   // 2.0f * kPI * eps2
             float sphi, cphi;
@@ -553,8 +671,7 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
             ++inoutRayCount;                                                              // :122
             if (defer && k == nlights - 1) {   // the last light: traced with the bounce ray
                 float omega = 2.0f * kPI * (1.0f - cosAMax);
-                F3 rdir = r_in.dir;
-                F3 nl = dot(rec.normal, rdir) < 0.0f ? rec.normal : -rec.normal;
+                F3 nl = dnl() < 0.0f ? rec.normal : -rec.normal;   // dot(rec.normal, rdir) < 0 (:128)
                 float d = dot(l, nl);
                 float mx = (0.0f < d) ? d : 0.0f;   // std::max(0.0f, d)
                 const float4 e = sc.mats[3 * i + 1];
@@ -582,8 +699,7 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
             sec_enter(sc, kSecLambert, false);
             if (lit) {   // HitWorld && hitID == i
                 float omega = 2.0f * kPI * (1.0f - cosAMax);
-                F3 rdir = r_in.dir;
-                F3 nl = dot(rec.normal, rdir) < 0.0f ? rec.normal : -rec.normal;
+                F3 nl = dnl() < 0.0f ? rec.normal : -rec.normal;   // dot(rec.normal, rdir) < 0 (:128)
                 float d = dot(l, nl);
                 float mx = (0.0f < d) ? d : 0.0f;   // std::max(0.0f, d)
                 const float4 e = sc.mats[3 * i + 1];
@@ -591,34 +707,84 @@ LRT_DEV F3 ScatterDir(const Material& mat, int matId, const Ray& r_in, const Hit
             }
         }
         return X;
-    } else if (mat.type == 1) {  // Metal :137-148
+    }
+    if constexpr (!kHead && !kDraws) {   // each branch's own code, as the source has it
+        if (mat.type == 1) {  // Metal :137-148
+            sec_count(sc, kSecMetal);
+            F3 refl = reflect(r_in.dir, rec.normal);
+            return refl + mat.roughness * RandomInUnitSphere(rng);
+        }
+        // Dielectric :149-193 (validate() admits types 0-2 only)
+        sec_count(sc, kSecDiel);
+        F3 outwardN;
+        F3 rdir = r_in.dir;
+        F3 refl = reflect(rdir, rec.normal);
+        float nint;
+        F3 refr = f3(0.0f, 0.0f, 0.0f);
+        float reflProb;
+        float cosine;
+        if (dot(rdir, rec.normal) > 0.0f) {
+            outwardN = -rec.normal;
+            nint = mat.ri;
+            cosine = dot(rdir, rec.normal);
+        } else {
+            outwardN = rec.normal;
+            nint = rcp_rn(mat.ri);
+            cosine = -dot(rdir, rec.normal);
+        }
+        if (refract(rdir, outwardN, nint, refr))
+            reflProb = schlick_with_r0(cosine, mat.roughness, sc.pow);   // the row's r0 = schlick_r0(mat.ri)
+        else
+            reflProb = 1.0f;
+        return RandomFloat01(rng) < reflProb ? refl : refr;
+    }
+    // Metal's and Dielectric's reflect (:139,:153), once for the lanes of both
+    F3 rdir = r_in.dir;
+    F3 refl = f3(0.0f, 0.0f, 0.0f);
+    if constexpr (kHead) refl = reflect_dn(rdir, rec.normal, dn);
+    if (mat.type == 1) {  // Metal :137-148
         sec_count(sc, kSecMetal);
-        F3 refl = reflect(r_in.dir, rec.normal);
-        return refl + mat.roughness * RandomInUnitSphere(rng);
+        if constexpr (!kHead) refl = reflect(rdir, rec.normal);
+        if constexpr (kDraws) {
+            rng = s3;
+            return refl + mat.roughness * InUnitSphereOf(k1, k2, k3, rng);
+        } else {
+            return refl + mat.roughness * RandomInUnitSphere(rng);
+        }
     }
     // Dielectric :149-193 (validate() admits types 0-2 only)
     sec_count(sc, kSecDiel);
+    if constexpr (!kHead) {
+        refl = reflect(rdir, rec.normal);
+        dn = dot(rdir, rec.normal);
+    }
     F3 outwardN;
-    F3 rdir = r_in.dir;
-    F3 refl = reflect(rdir, rec.normal);
     float nint;
     F3 refr = f3(0.0f, 0.0f, 0.0f);
     float reflProb;
     float cosine;
-    if (dot(rdir, rec.normal) > 0.0f) {
+    if (dn > 0.0f) {   // dot(rdir, rec.normal) > 0
         outwardN = -rec.normal;
         nint = mat.ri;
-        cosine = dot(rdir, rec.normal);
+        cosine = dn;
     } else {
         outwardN = rec.normal;
         nint = rcp_rn(mat.ri);
-        cosine = -dot(rdir, rec.normal);
+        cosine = -dn;
     }
-    if (refract(rdir, outwardN, nint, refr))
+    bool refracts;
+    if constexpr (kHead) refracts = refract_dt(rdir, outwardN, dn > 0.0f ? -dn : dn, nint, refr);
+    else refracts = refract(rdir, outwardN, nint, refr);
+    if (refracts)
         reflProb = schlick_with_r0(cosine, mat.roughness, sc.pow);   // the row's r0 = schlick_r0(mat.ri)
     else
         reflProb = 1.0f;
-    return RandomFloat01(rng) < reflProb ? refl : refr;
+    if constexpr (kDraws) {
+        rng = s1;
+        return k1 * (1.0f / 16777216.0f) < reflProb ? refl : refr;   // RandomFloat01() < reflProb
+    } else {
+        return RandomFloat01(rng) < reflProb ? refl : refr;
+    }
 }
 
 // Scatter in the reference's shape (parallel.cpp:78-196): the attenuation, the scattered
