@@ -163,17 +163,17 @@ static int denoise_device(const lrt_denoise_desc* d, const float* color, const l
     }
     DenoiseArgs a;
     memset(&a, 0, sizeof(a));
-    a.std = g ? reinterpret_cast<const float4*>(g->color_std) : nullptr;
-    a.nrm = g ? reinterpret_cast<const float4*>(g->normal) : nullptr;
-    a.pos = g ? reinterpret_cast<const float4*>(g->world_pos) : nullptr;
-    a.alb = g ? reinterpret_cast<const float4*>(g->albedo) : nullptr;
+    a.std = g ? quads(g->color_std) : nullptr;
+    a.nrm = g ? quads(g->normal) : nullptr;
+    a.pos = g ? quads(g->world_pos) : nullptr;
+    a.alb = g ? quads(g->albedo) : nullptr;
     a.w = d->width;
     a.h = d->height;
     const float rl2e = sqrtf(1.44269504f);
     a.kn = rl2e / d->sigma_normal;
     a.kx = rl2e / d->sigma_pos;
     a.ka = rl2e / d->sigma_albedo;
-    const float4* src = reinterpret_cast<const float4*>(color);
+    const float4* src = quads(color);
     if (K == 1 && out == color) {
         LRT_HIP(hipMemcpyAsync(tmp[0], color, npix * sizeof(float4), hipMemcpyDeviceToDevice, s));
         src = tmp[0];
@@ -182,7 +182,7 @@ static int denoise_device(const lrt_denoise_desc* d, const float* color, const l
         const bool last = k == K - 1;
         const float sc = d->sigma_color / (float)(1 << k);
         a.in = src;
-        a.out = last ? reinterpret_cast<float4*>(out) : tmp[k & 1];
+        a.out = last ? quads(out) : tmp[k & 1];
         a.s = 1 << k;
         a.sc2 = sc * sc;
         a.rgb_only = last;
@@ -212,9 +212,7 @@ using namespace lrt;
 extern "C" {
 
 int lrt_denoise_default(int width, int height, lrt_denoise_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (int rc = frame_default_begin(out, sizeof(*out), width, height)) return rc;
     out->width = width;
     out->height = height;
     out->iterations = LRT_DENOISE_MAX_ITER;

@@ -8,6 +8,7 @@
 // only the planes asked for (uniform branches on the plane pointers). No contraction, like the
 // render units: id and depth are pinned bit for bit to lrt_accel_eval.
 #include "lrt_internal.h"
+#include "lrt_pixel.h"
 
 namespace lrt {
 
@@ -35,19 +36,16 @@ struct GbufferArgs {
 
 constexpr int kSceneOff = 0, kSceneScratch = 1, kSceneInline = 2;   // gbuffer_pixel's kScene
 
-// A wave covers 8 x 8 pixels and a workgroup of four waves 32 x 8 (lrt_temporal.hip's shape):
-// coherent primary rays keep the grid walk's cells and the scan's exits together, and a float4 store
-// of the wave is eight whole 128 B lines. Timed against waves of 32 x 2 pixels in the same workgroup
-// at 1280 x 720 over random_scene(1000, 1), all six planes, alternating in one process: 0.0242 ms
-// against 0.0250 ms, twice each.
-constexpr int kBlockW = 32, kBlockH = 8;
-
+// lrt_pixel.h's map, 8 x 8 pixels per wave: coherent primary rays keep the grid walk's cells and the
+// scan's exits together, and a float4 store of the wave is eight whole 128 B lines. Timed against
+// waves of 32 x 2 pixels in the same workgroup at 1280 x 720 over random_scene(1000, 1), all six
+// planes, alternating in one process: 0.0242 ms against 0.0250 ms, twice each.
+//
 // One pixel. kGrid: the uniform grid (else the scan). kScene: an lrt_scene_motion was given, its
 // packed arrays at a.msph / a.mpsph or in the kernel's own arguments at isph.
 template <bool kGrid, int kScene>
 __device__ __forceinline__ void gbuffer_pixel(const GbufferArgs& a, const float4* isph = nullptr) {
-    const int l = threadIdx.x;   // wave l / 64, its lane's pixel (l % 8, l / 8 % 8)
-    const int x = blockIdx.x * kBlockW + (l >> 6) * 8 + (l & 7), y = blockIdx.y * kBlockH + ((l >> 3) & 7);
+    const int x = block_x(), y = block_y();
     if (x >= a.w || y >= a.h) return;
     const size_t ip = (size_t)y * a.w + x;
     const float s = ((float)x + 0.5f) * a.rw, t = ((float)y + 0.5f) * a.rh;
@@ -109,12 +107,12 @@ __device__ __forceinline__ void gbuffer_pixel(const GbufferArgs& a, const float4
 }
 
 template <bool kGrid, bool kScene>
-__global__ __launch_bounds__(kBlockW* kBlockH) void gbuffer_kernel(GbufferArgs a) {
+__global__ __launch_bounds__(kPixBlockW* kPixBlockH) void gbuffer_kernel(GbufferArgs a) {
     gbuffer_pixel<kGrid, kScene ? kSceneScratch : kSceneOff>(a);
 }
 // ... with the two scenes' spheres in the arguments (count <= kInlineSpheres).
 template <bool kGrid>
-__global__ __launch_bounds__(kBlockW* kBlockH) void gbuffer_inline_kernel(GbufferArgs a, InlineSpheres sc) {
+__global__ __launch_bounds__(kPixBlockW* kPixBlockH) void gbuffer_inline_kernel(GbufferArgs a, InlineSpheres sc) {
     gbuffer_pixel<kGrid, kSceneInline>(a, sc.v);
 }
 
@@ -179,10 +177,10 @@ static int gbuffer_device(const lrt_gbuffer_desc* d, const lrt_scene_motion* sm,
     if (grid && !c.grid_built) return fail(LRT_E_STATE, "the grid is not built");
     GbufferArgs a;
     memset(&a, 0, sizeof(a));
-    a.normal = reinterpret_cast<float4*>(o->normal);
-    a.pos = reinterpret_cast<float4*>(o->world_pos);
-    a.alb = reinterpret_cast<float4*>(o->albedo);
-    a.motion = reinterpret_cast<float4*>(o->motion);
+    a.normal = quads(o->normal);
+    a.pos = quads(o->world_pos);
+    a.alb = quads(o->albedo);
+    a.motion = quads(o->motion);
     a.id = o->id;
     a.depth = o->depth;
     a.w = d->width;
@@ -219,8 +217,8 @@ static int gbuffer_device(const lrt_gbuffer_desc* d, const lrt_scene_motion* sm,
         if (int rc = upload_motion(sm, s, "gbuffer scratch", &a.msph)) return rc;
         a.mpsph = a.msph + sm->count;
     }
-    const dim3 g((unsigned)((a.w + kBlockW - 1) / kBlockW), (unsigned)((a.h + kBlockH - 1) / kBlockH));
-    const int b = kBlockW * kBlockH;
+    const dim3 g = pixel_grid(a.w, a.h);
+    const int b = kPixBlockW * kPixBlockH;
     if (inl) {
         InlineSpheres sc;
         memset(&sc, 0, sizeof(sc));
@@ -246,10 +244,8 @@ extern "C" {
 
 int lrt_gbuffer_default(int width, int height, const lrt_camera* camera, const lrt_camera* prev_camera,
                         lrt_gbuffer_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (!camera) return fail(LRT_E_INVALID, "camera is NULL");
-    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (out && !camera) return fail(LRT_E_INVALID, "camera is NULL");
+    if (int rc = frame_default_begin(out, sizeof(*out), width, height)) return rc;
     out->width = width;
     out->height = height;
     out->camera = *camera;
@@ -277,27 +273,17 @@ int lrt_gbuffer_host(const lrt_gbuffer_desc* desc, const lrt_scene_motion* scene
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     hipStream_t s = ctx().stream;
-    // Every plane asked for gets a device mirror, all in one allocation that lives for the call
-    // (the four RGBA planes first: every mirror stays 16 B aligned).
+    // every plane asked for gets a device mirror; none is copied in (whole planes are written)
     Plane pl[6];
     planes_of(desc, out, pl);
-    size_t total = 0;
-    for (const Plane& q : pl) total += q.p ? q.bytes : 0;
-    DeviceStaging<char> m;
-    if (hipMalloc(&m.p, total) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(gbuffer staging)");
-    void* dev[6];
-    size_t off = 0;
-    for (int i = 0; i < 6; ++i) {
-        dev[i] = pl[i].p ? m.p + off : nullptr;
-        off += pl[i].p ? pl[i].bytes : 0;
-    }
-    const lrt_gbuffer d_out = {(float*)dev[0], (float*)dev[1], (float*)dev[2], (float*)dev[3], (int32_t*)dev[4],
-                               (float*)dev[5]};
+    HostMirrors m;
+    int at[6];
+    for (int i = 0; i < 6; ++i) at[i] = m.out(const_cast<void*>(pl[i].p), pl[i].bytes);
+    if (int rc = m.alloc("hipMalloc(gbuffer staging)")) return rc;
+    const lrt_gbuffer d_out = {m.dev<float>(at[0]), m.dev<float>(at[1]), m.dev<float>(at[2]),
+                               m.dev<float>(at[3]), m.dev<int32_t>(at[4]), m.dev<float>(at[5])};
     if (int rc = gbuffer_device(desc, scene, &d_out, s)) return rc;
-    for (int i = 0; i < 6; ++i)
-        if (pl[i].p) LRT_HIP(hipMemcpyAsync(const_cast<void*>(pl[i].p), dev[i], pl[i].bytes, hipMemcpyDeviceToHost, s));
-    LRT_HIP(hipStreamSynchronize(s));
-    return LRT_OK;
+    return m.download(s);
 }
 
 }  // extern "C"

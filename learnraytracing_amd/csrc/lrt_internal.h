@@ -12,7 +12,9 @@
 //   lrt_denoise.hip   the feature-guided a-trous denoiser (lrt_denoise_*): kernel and entry points
 //   lrt_temporal.hip  temporal reprojection and accumulation (lrt_temporal_*): kernel and entry points
 //   lrt_temporal_gbuffer.hip  the step driven by the G-buffer's ids and motion (lrt_temporal_accumulate_gbuffer_*)
-//   lrt_temporal_blend.h      steps 6 and 7 of the temporal rule, shared by the two units above
+//   lrt_temporal_blend.h      steps 6 and 7 of the temporal rule and the color_std store, shared by the temporal units
+//   lrt_pixel.h       the pixel map, launch grid and colour store of the one-thread-per-pixel post-process kernels
+//   lrt_staging.h     the layout of a *_host call's device mirrors (plain C++; HostMirrors below runs on it)
 //   lrt_svgf.hip      the variance-guided filter over the temporal state (lrt_svgf_*): kernels and entry points
 //   lrt_tonemap.hip   auto-exposure metering and tone mapping (lrt_tonemap_*): kernels and entry points
 //   lrt_gbuffer.hip   the pixel-centre G-buffer pass (lrt_gbuffer_*): kernel and entry points
@@ -22,10 +24,11 @@
 //   lrt_atrous.h      the lattice tile of the two a-trous kernels (denoise, svgf): geometry, anchor, staging, taps
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
-// The host plumbing that the post-process units (denoise, temporal, svgf, tonemap, gbuffer) share is
-// below: the size and aliasing checks, the staging allocation of a *_host call, the stream scratch
-// of a *_device call, the ready check, and the two-scene sphere arrays (lrt_scene_motion) of the
-// temporal and the G-buffer kernels.
+// The host plumbing that the post-process units (denoise, temporal, temporal_gbuffer, svgf, tonemap,
+// gbuffer, upsample, temporal_upsample, rectify) share is below: the size, range, pairing and
+// aliasing checks, the opening of a *_default function, the device mirrors of a *_host call
+// (HostMirrors), the stream scratch of a *_device call, the ready check, and the two-scene sphere
+// arrays (lrt_scene_motion) of the temporal and the G-buffer kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -49,6 +52,7 @@
 
 #include "lrt.h"
 #include "lrt_diag.h"
+#include "lrt_staging.h"
 #include "lrt_trace.h"
 
 #define LRT_VERSION_STRING "lrt-mi355x 0.4.0 gfx950"
@@ -444,14 +448,43 @@ unsigned long long* secstats_buffer(hipStream_t s);
 void secstats_dump(const unsigned long long* d_sec, hipStream_t s);
 #endif
 
-// ---- the post-process units (lrt_denoise, lrt_temporal, lrt_svgf, lrt_tonemap). The strings are
-// part of the ABI (lrt_last_error()).
+// ---- the post-process units (lrt_denoise, lrt_temporal, lrt_temporal_gbuffer, lrt_svgf, lrt_tonemap,
+// lrt_gbuffer, lrt_upsample, lrt_temporal_upsample, lrt_rectify). The strings are part of the ABI
+// (lrt_last_error()); each validator calls these in the order its checks have always had.
 // A frame of width x height pixels whose float count fits an int.
 inline int validate_frame_size(int width, int height) {
     if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
     if ((long long)width * height > INT_MAX / 4) return fail(LRT_E_INVALID, "image too large");
     return LRT_OK;
 }
+// How a lrt_*_default function begins: out and the size checked (a unit with a low frame passes
+// the smaller of each pair), then the descriptor zeroed.
+inline int frame_default_begin(void* out, size_t bytes, int width, int height) {
+    if (!out) return fail(LRT_E_INVALID, "out is NULL");
+    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
+    memset(out, 0, bytes);
+    return LRT_OK;
+}
+inline int validate_min_history(int min_history) {
+    return min_history < 1 ? fail(LRT_E_INVALID, "min_history must be >= 1") : LRT_OK;
+}
+inline int validate_alpha_min(float alpha_min) {
+    return alpha_min > 0.0f && alpha_min <= 1.0f ? LRT_OK : fail(LRT_E_INVALID, "alpha_min must be in (0, 1]");
+}
+inline int validate_normal_min(float normal_min) {
+    return normal_min >= -1.0f && normal_min <= 1.0f ? LRT_OK : fail(LRT_E_INVALID, "normal_min must be in [-1, 1]");
+}
+// The history of a step driven by the G-buffer: a state and the G-buffer it was made under, both
+// or neither, each with the members that are read.
+inline int validate_history_pair(const lrt_temporal_state* prev, const lrt_gbuffer* prev_g) {
+    if (!prev != !prev_g) return fail(LRT_E_INVALID, "prev and prev_g must both be given, or neither");
+    if (prev && (!prev->color || !prev->moment2)) return fail(LRT_E_INVALID, "prev needs color and moment2");
+    if (prev_g && (!prev_g->normal || !prev_g->id)) return fail(LRT_E_INVALID, "prev_g needs normal and id");
+    return LRT_OK;
+}
+// float planes as the kernels take them
+inline const float4* quads(const float* p) { return reinterpret_cast<const float4*>(p); }
+inline float4* quads(float* p) { return reinterpret_cast<float4*>(p); }
 // Do the byte ranges [p, p + bytes_p) and [q, q + bytes_q) share a byte? A null pointer: no.
 inline bool ranges_overlap(const void* p, size_t bytes_p, const void* q, size_t bytes_q) {
     const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
@@ -473,15 +506,62 @@ inline int spans_alias(const Span* outs, int nout, const Span* ins, int nin) {
     }
     return 0;
 }
+// A G-buffer overwritten in place is no history: the current one's normal and id against the
+// previous one's (null spans where there is none).
+inline int validate_gbuffer_kept(const Span& normal, const Span& id, const Span& prev_normal, const Span& prev_id) {
+    for (const Span& c : {normal, id})
+        for (const Span& p : {prev_normal, prev_id})
+            if (ranges_overlap(c.p, c.bytes, p.p, p.bytes))
+                return fail(LRT_E_INVALID, "aliasing: cur's normal or id overlaps prev_g's");
+    return LRT_OK;
+}
 // Context 0 is initialised (the caller holds g_mu).
 inline int require_initialized() {
     return g_devs[0].ready ? LRT_OK : fail(LRT_E_STATE, "lrt_initialize() has not been called");
 }
-// One device allocation that lives for a *_host call: the mirrors of its buffers.
-template <class T>
-struct DeviceStaging {
-    T* p = nullptr;
-    ~DeviceStaging() { if (p) (void)hipFree(p); }
+// The device mirrors of a *_host call's buffers, in one allocation that lives for the call
+// (lrt_staging.h places them). The call lists its buffers -- in() is only read, out() only written,
+// inout() an output of which a part survives the call (an alpha the kernel leaves, a buffer updated
+// in place) and which is therefore copied in first; a null pointer is a buffer that is not given or
+// not read, with no mirror -- then alloc(), upload(), its *_device function on dev<T>(i), download().
+struct HostMirrors {
+    StagingPlan plan;
+    char* base = nullptr;
+    bool full = false;
+    ~HostMirrors() { if (base) (void)hipFree(base); }
+    int add(const void* host_in, void* host_out, size_t bytes) {
+        const int i = plan.add(host_in, host_out, bytes);
+        full = full || i < 0;
+        return i;
+    }
+    int in(const void* p, size_t bytes) { return add(p, nullptr, bytes); }
+    int out(void* p, size_t bytes) { return add(nullptr, p, bytes); }
+    int inout(void* p, size_t bytes) { return add(p, p, bytes); }
+    // what: the unit's out-of-memory string
+    int alloc(const char* what) {
+        if (full) return fail(LRT_E_STATE, "staging: more buffers than StagingPlan::kCapacity");
+        if (hipMalloc(&base, plan.total()) != hipSuccess) {
+            base = nullptr;
+            return fail(LRT_E_NOMEM, what);
+        }
+        return LRT_OK;
+    }
+    template <class T>
+    T* dev(int i) const { return plan.present(i) ? reinterpret_cast<T*>(base + plan.offset(i)) : nullptr; }
+    int upload(hipStream_t s) const {
+        for (int i = 0; i < plan.count; ++i)
+            if (const void* h = plan.item[i].host_in)
+                LRT_HIP(hipMemcpyAsync(base + plan.offset(i), h, plan.item[i].bytes, hipMemcpyHostToDevice, s));
+        return LRT_OK;
+    }
+    // ... and waits for the stream: the call's one synchronisation
+    int download(hipStream_t s) const {
+        for (int i = 0; i < plan.count; ++i)
+            if (void* h = plan.item[i].host_out)
+                LRT_HIP(hipMemcpyAsync(h, base + plan.offset(i), plan.item[i].bytes, hipMemcpyDeviceToHost, s));
+        LRT_HIP(hipStreamSynchronize(s));
+        return LRT_OK;
+    }
 };
 // At least `bytes` of stream s's scratch (stream_scratch), its failure as an lrt_* code.
 inline int scratch_or_fail(hipStream_t s, size_t bytes, const char* what, void** out) {

@@ -118,18 +118,9 @@ __global__ __launch_bounds__(kRectW* kRectH) void rectify_kernel(RectifyArgs a) 
         cls = any ? 1 : 0;
     }
     const size_t io = (size_t)y * a.w + x;
-    float* const po = reinterpret_cast<float*>(a.oc + io);   // 12 B: the alpha stays
-    po[0] = col.x;
-    po[1] = col.y;
-    po[2] = col.z;
+    write_rgb(a.oc, io, col);
     a.om[io] = make_float4(m2.x, m2.y, m2.z, n);
-    if (a.ostd) {
-        const float3 sd = temporal_std(col, m2, n, a.short_std, a.min_history);
-        float* const os = reinterpret_cast<float*>(a.ostd + io);
-        os[0] = sd.x;
-        os[1] = sd.y;
-        os[2] = sd.z;
-    }
+    write_std(a.ostd, io, col, m2, n, a.short_std, a.min_history);
     if (a.ocls) a.ocls[io] = cls;
 }
 
@@ -147,7 +138,7 @@ static int validate_rectify(const lrt_rectify_desc* d, const float* ref, const i
     if (d->radius < 1 || d->radius > LRT_RECTIFY_MAX_RADIUS) return fail(LRT_E_INVALID, "radius must be in 1..3");
     const int side = 2 * d->radius + 1;
     if (d->min_taps < 1 || d->min_taps > side * side) return fail(LRT_E_INVALID, "min_taps must be in 1..(2 radius + 1)^2");
-    if (d->min_history < 1) return fail(LRT_E_INVALID, "min_history must be >= 1");
+    if (int rc = validate_min_history(d->min_history)) return rc;
     for (float v : {d->ref_scale, d->gamma, d->range_floor, d->reset_history, d->short_std})
         if (!std::isfinite(v)) return fail(LRT_E_INVALID, "parameters must be finite");
     if (!(d->ref_scale > 0.0f) || !(d->range_floor > 0.0f) || !(d->short_std > 0.0f))
@@ -176,13 +167,13 @@ static int rectify_device(const lrt_rectify_desc* d, const float* ref, const int
                           const lrt_temporal_state* out, float* std, int32_t* cls, hipStream_t s) {
     RectifyArgs a;
     memset(&a, 0, sizeof(a));
-    a.ref = reinterpret_cast<const float4*>(ref);
+    a.ref = quads(ref);
     a.id = id;
-    a.sc = reinterpret_cast<const float4*>(state->color);
-    a.sm = reinterpret_cast<const float4*>(state->moment2);
-    a.oc = reinterpret_cast<float4*>(out->color);
-    a.om = reinterpret_cast<float4*>(out->moment2);
-    a.ostd = reinterpret_cast<float4*>(std);
+    a.sc = quads(state->color);
+    a.sm = quads(state->moment2);
+    a.oc = quads(out->color);
+    a.om = quads(out->moment2);
+    a.ostd = quads(std);
     a.ocls = cls;
     a.w = d->width;
     a.h = d->height;
@@ -210,9 +201,7 @@ using namespace lrt;
 extern "C" {
 
 int lrt_temporal_rectify_default(int width, int height, lrt_rectify_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (int rc = frame_default_begin(out, sizeof(*out), width, height)) return rc;
     out->width = width;
     out->height = height;
     out->radius = 2;
@@ -246,36 +235,23 @@ int lrt_temporal_rectify_host(const lrt_rectify_desc* desc, const float* ref, co
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     hipStream_t s = ctx().stream;
-    // Every buffer goes through a device mirror of its own (a call in place on the host runs out of
-    // place on the device: the same bits), all in one allocation that lives for the call: six RGBA
-    // frames (3 inputs, 3 outputs), then the id and the class plane, so that every mirror stays 16 B
-    // aligned. The two outputs whose alpha stays are copied in first.
+    // Every buffer goes through a device mirror of its own: a call in place on the host has two
+    // mirrors of each state frame and runs out of place on the device (the same bits). The two
+    // outputs whose alpha stays (out->color, color_std) are copied in first.
     const size_t px = (size_t)desc->width * desc->height, quad = 16 * px, word = 4 * px;
-    const float* const hin[3] = {ref, state->color, state->moment2};
-    float* const hout[3] = {out->color, out->moment2, color_std};
-    DeviceStaging<char> m;
-    if (hipMalloc(&m.p, 6 * quad + 2 * word) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(rectify staging)");
-    float* din[3];
-    float* dout[3];
-    for (int i = 0; i < 3; ++i) {
-        din[i] = reinterpret_cast<float*>(m.p + i * quad);
-        LRT_HIP(hipMemcpyAsync(din[i], hin[i], quad, hipMemcpyHostToDevice, s));
-    }
-    int32_t* const did = reinterpret_cast<int32_t*>(m.p + 6 * quad);
-    int32_t* const dcls = class_out ? reinterpret_cast<int32_t*>(m.p + 6 * quad + word) : nullptr;
-    LRT_HIP(hipMemcpyAsync(did, id, word, hipMemcpyHostToDevice, s));
-    for (int i = 0; i < 3; ++i) {
-        dout[i] = hout[i] ? reinterpret_cast<float*>(m.p + (3 + i) * quad) : nullptr;
-        if (hout[i] && i != 1) LRT_HIP(hipMemcpyAsync(dout[i], hout[i], quad, hipMemcpyHostToDevice, s));
-    }
-    const lrt_temporal_state dstate = {din[1], din[2], nullptr, nullptr, nullptr};
-    const lrt_temporal_state dnext = {dout[0], dout[1], nullptr, nullptr, nullptr};
-    if (int rc = rectify_device(desc, din[0], did, &dstate, &dnext, dout[2], dcls, s)) return rc;
-    for (int i = 0; i < 3; ++i)
-        if (hout[i]) LRT_HIP(hipMemcpyAsync(hout[i], dout[i], quad, hipMemcpyDeviceToHost, s));
-    if (class_out) LRT_HIP(hipMemcpyAsync(class_out, dcls, word, hipMemcpyDeviceToHost, s));
-    LRT_HIP(hipStreamSynchronize(s));
-    return LRT_OK;
+    HostMirrors m;
+    const int ref_ = m.in(ref, quad), id_ = m.in(id, word);
+    const int scolor_ = m.in(state->color, quad), smoment_ = m.in(state->moment2, quad);
+    const int ocolor_ = m.inout(out->color, quad), omoment_ = m.out(out->moment2, quad), std_ = m.inout(color_std, quad);
+    const int class_ = m.out(class_out, word);
+    if (int rc = m.alloc("hipMalloc(rectify staging)")) return rc;
+    if (int rc = m.upload(s)) return rc;
+    auto f = [&m](int i) { return m.dev<float>(i); };
+    const lrt_temporal_state dstate = {f(scolor_), f(smoment_), nullptr, nullptr, nullptr};
+    const lrt_temporal_state dnext = {f(ocolor_), f(omoment_), nullptr, nullptr, nullptr};
+    if (int rc = rectify_device(desc, f(ref_), m.dev<int32_t>(id_), &dstate, &dnext, f(std_), m.dev<int32_t>(class_), s))
+        return rc;
+    return m.download(s);
 }
 
 }  // extern "C"

@@ -278,7 +278,7 @@ static int validate_svgf(const lrt_svgf_desc* d, const float* color, const float
     if (d->iterations < 1 || d->iterations > LRT_SVGF_MAX_ITER)
         return fail(LRT_E_INVALID, "iterations must be in 1..LRT_SVGF_MAX_ITER");
     if (d->flags != 0 || d->reserved != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
-    if (d->min_history < 1) return fail(LRT_E_INVALID, "min_history must be >= 1");
+    if (int rc = validate_min_history(d->min_history)) return rc;
     for (float v : {d->sigma_color, d->sigma_normal, d->sigma_pos, d->albedo_floor})
         if (!std::isfinite(v) || !(v > 0.0f))
             return fail(LRT_E_INVALID, "sigmas and albedo_floor must be finite and > 0");
@@ -311,14 +311,13 @@ static int svgf_device(const lrt_svgf_desc* d, const float* color, const float* 
     float4* const tv[2] = {base + npix, ntmp == 4 ? base + 3 * npix : nullptr};
     SvgfArgs a;
     memset(&a, 0, sizeof(a));
-    auto q = [](const float* f) { return reinterpret_cast<const float4*>(f); };
-    a.cin = q(color);
-    a.vin = q(moment2);
+    a.cin = quads(color);
+    a.vin = quads(moment2);
     a.cout = tc[0];
     a.vout = tv[0];
-    a.nrm = g && g->normal ? q(g->normal) : nullptr;
-    a.pos = g && g->world_pos ? q(g->world_pos) : nullptr;
-    a.alb = g && g->albedo ? q(g->albedo) : nullptr;
+    a.nrm = g && g->normal ? quads(g->normal) : nullptr;
+    a.pos = g && g->world_pos ? quads(g->world_pos) : nullptr;
+    a.alb = g && g->albedo ? quads(g->albedo) : nullptr;
     a.has_n = a.nrm != nullptr;
     a.has_x = a.pos != nullptr;
     a.has_a = a.alb != nullptr;
@@ -340,8 +339,8 @@ static int svgf_device(const lrt_svgf_desc* d, const float* color, const float* 
         const bool last = k == K - 1;
         a.cin = tc[k & 1];
         a.vin = tv[k & 1];
-        a.cout = last ? reinterpret_cast<float4*>(out) : tc[(k + 1) & 1];
-        a.vout = last ? reinterpret_cast<float4*>(var) : tv[(k + 1) & 1];
+        a.cout = last ? quads(out) : tc[(k + 1) & 1];
+        a.vout = last ? quads(var) : tv[(k + 1) & 1];
         if (!a.has_n) a.nrm = a.cin;
         if (!a.has_x) a.pos = a.cin;
         if (!a.has_a) a.alb = a.cin;
@@ -360,9 +359,7 @@ using namespace lrt;
 extern "C" {
 
 int lrt_svgf_default(int width, int height, lrt_svgf_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (int rc = frame_default_begin(out, sizeof(*out), width, height)) return rc;
     out->width = width;
     out->height = height;
     out->iterations = LRT_SVGF_MAX_ITER;
@@ -391,41 +388,27 @@ int lrt_svgf_filter_host(const lrt_svgf_desc* desc, const float* color, const fl
     std::lock_guard<std::mutex> lk(g_mu);
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
-    const size_t bytes = (size_t)desc->width * desc->height * 4 * sizeof(float);
+    const size_t quad = (size_t)desc->width * desc->height * 4 * sizeof(float);
     hipStream_t s = ctx().stream;
-    // Every buffer goes through a device mirror of its own, all in one allocation that lives for
-    // the call: 5 inputs, 2 outputs (copied in first: their alphas stay). In place, out's mirror
-    // is color's.
-    const float* const hin[5] = {color, moment2, guides ? guides->normal : nullptr,
-                                 guides ? guides->world_pos : nullptr, guides ? guides->albedo : nullptr};
-    DeviceStaging<float> m;
-    if (hipMalloc(&m.p, 7 * bytes) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(svgf staging)");
-    const size_t quad = bytes / sizeof(float);
-    float* din[5];
-    for (int i = 0; i < 5; ++i) {
-        din[i] = hin[i] ? m.p + i * quad : nullptr;
-        if (hin[i]) LRT_HIP(hipMemcpyAsync(din[i], hin[i], bytes, hipMemcpyHostToDevice, s));
-    }
-    float* d_out = din[0];
-    if (out != color) {
-        d_out = m.p + 5 * quad;
-        LRT_HIP(hipMemcpyAsync(d_out, out, bytes, hipMemcpyHostToDevice, s));
-    }
-    float* d_var = nullptr;
-    if (variance_out) {
-        d_var = m.p + 6 * quad;
-        LRT_HIP(hipMemcpyAsync(d_var, variance_out, bytes, hipMemcpyHostToDevice, s));
-    }
+    // Every buffer that is given goes through a device mirror of its own. The two outputs are copied
+    // in first (their alphas stay); in place, out's mirror is color's.
+    const bool in_place = out == color;
+    HostMirrors m;
+    const int color_ = m.add(color, in_place ? out : nullptr, quad), moment_ = m.in(moment2, quad);
+    const int normal_ = m.in(guides ? guides->normal : nullptr, quad);
+    const int pos_ = m.in(guides ? guides->world_pos : nullptr, quad);
+    const int albedo_ = m.in(guides ? guides->albedo : nullptr, quad);
+    const int out_ = in_place ? color_ : m.inout(out, quad), var_ = m.inout(variance_out, quad);
+    if (int rc = m.alloc("hipMalloc(svgf staging)")) return rc;
+    if (int rc = m.upload(s)) return rc;
+    auto f = [&m](int i) { return m.dev<float>(i); };
     lrt_features dg;
     memset(&dg, 0, sizeof(dg));
-    dg.normal = din[2];
-    dg.world_pos = din[3];
-    dg.albedo = din[4];
-    if (int rc = svgf_device(desc, din[0], din[1], &dg, d_out, d_var, s)) return rc;
-    LRT_HIP(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, s));
-    if (variance_out) LRT_HIP(hipMemcpyAsync(variance_out, d_var, bytes, hipMemcpyDeviceToHost, s));
-    LRT_HIP(hipStreamSynchronize(s));
-    return LRT_OK;
+    dg.normal = f(normal_);
+    dg.world_pos = f(pos_);
+    dg.albedo = f(albedo_);
+    if (int rc = svgf_device(desc, f(color_), f(moment_), &dg, f(out_), f(var_), s)) return rc;
+    return m.download(s);
 }
 
 }  // extern "C"

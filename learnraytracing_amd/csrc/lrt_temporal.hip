@@ -61,12 +61,7 @@ LRT_DEV float3 mad3(const float s, const float3 a, const float3 b) {   // s a + 
     return make_float3(s * a.x + b.x, s * a.y + b.y, s * a.z + b.z);
 }
 
-// A wave covers 8 x 8 pixels and a workgroup of four waves 32 x 8: a streamed access of a wave is
-// eight whole 128 B lines, and its gathers stay within about nine rows of the previous state
-// whatever the direction of the motion. Timed against waves of 64 x 1 pixels in blocks of 64 x 4
-// (the denoiser's shape), alternating in one process: 3 % faster on the orbit, 6 % under a static
-// camera.
-constexpr int kBlockW = 32, kBlockH = 8;
+// (the pixel map, 8 x 8 pixels per wave, and why: lrt_pixel.h)
 constexpr int kMatchBatch = 4;   // spheres per trip of the moving form's match loop
 
 // One pixel of the step. kHist: there is a previous state (else every pixel is reset). kMove: the
@@ -77,8 +72,7 @@ __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const Moti
                                                const float4* isph = nullptr) {
     const float4* const sph = kMove == kMoveInline ? isph : m.sph;
     const float4* const psph = kMove == kMoveInline ? isph + m.count : m.psph;
-    const int t = threadIdx.x;   // wave t / 64, its lane's pixel (t % 8, t / 8 % 8)
-    const int x = blockIdx.x * kBlockW + (t >> 6) * 8 + (t & 7), y = blockIdx.y * kBlockH + ((t >> 3) & 7);
+    const int x = block_x(), y = block_y();
     if (x >= a.w || y >= a.h) return;
     const size_t ip = (size_t)y * a.w + x;
     const float k = a.k;
@@ -203,37 +197,28 @@ __device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const Moti
             m2 = make_float3(be * sm.x + al * m2.x, be * sm.y + al * m2.y, be * sm.z + al * m2.z);
         }
     }
-    float* const oc = reinterpret_cast<float*>(a.oc + ip);   // 12 B: the alpha stays
-    oc[0] = col.x;
-    oc[1] = col.y;
-    oc[2] = col.z;
+    write_rgb(a.oc, ip, col);
     a.om[ip] = make_float4(m2.x, m2.y, m2.z, n);
     a.on[ip] = make_float4(N.x, N.y, N.z, 0.0f);
     a.ox[ip] = make_float4(X.x, X.y, X.z, 0.0f);
     if (a.oa) a.oa[ip] = make_float4(k * a4.x, k * a4.y, k * a4.z, 0.0f);
-    if (a.ostd) {
-        const float3 sd = temporal_std(col, m2, n, a.short_std, a.min_history);
-        float* const os = reinterpret_cast<float*>(a.ostd + ip);
-        os[0] = sd.x;
-        os[1] = sd.y;
-        os[2] = sd.z;
-    }
+    write_std(a.ostd, ip, col, m2, n, a.short_std, a.min_history);
     if (kMove && m.motion) m.motion[ip] = mv;
 }
 
 template <bool kHist>
-__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_kernel(TemporalArgs a) {
+__global__ __launch_bounds__(kPixBlockW* kPixBlockH) void temporal_kernel(TemporalArgs a) {
     temporal_pixel<kHist, kMoveOff>(a, MotionArgs{});
 }
 
 // The moving form: the same block of 8 x 8-pixel waves.
 template <bool kHist>
-__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_moving_kernel(TemporalArgs a, MotionArgs m) {
+__global__ __launch_bounds__(kPixBlockW* kPixBlockH) void temporal_moving_kernel(TemporalArgs a, MotionArgs m) {
     temporal_pixel<kHist, kMoveScratch>(a, m);
 }
 
 // ... with the spheres in the arguments (count <= kInlineSpheres).
-__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_moving_inline_kernel(TemporalArgs a, MotionArgs m,
+__global__ __launch_bounds__(kPixBlockW* kPixBlockH) void temporal_moving_inline_kernel(TemporalArgs a, MotionArgs m,
                                                                                   InlineSpheres sc) {
     temporal_pixel<true, kMoveInline>(a, m, sc.v);
 }
@@ -241,6 +226,21 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_moving_inline_kerne
 static float3 f3(const lrt_float3& v) { return make_float3(v.x, v.y, v.z); }
 static float hdot(const float3 a, const float3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 static float3 hsub(const float3 a, const float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
+
+// A step's buffers as the aliasing checks see them: the 9 inputs (the previous state's among them),
+// then the 6 outputs.
+struct TemporalSpans {
+    Span v[15];
+    TemporalSpans(const lrt_temporal_desc* d, const float* color, const lrt_features* cur, const lrt_temporal_state* prev,
+                  const lrt_temporal_state* next, const float* std) {
+        const lrt_temporal_state none = {};
+        const lrt_temporal_state& p = prev ? *prev : none;
+        const float* const all[15] = {color, cur->normal, cur->world_pos, cur->albedo, p.color, p.moment2, p.normal,
+                                      p.world_pos, p.albedo, next->color, next->moment2, next->normal, next->world_pos,
+                                      next->albedo, std};
+        for (int i = 0; i < 15; ++i) v[i] = {all[i], (size_t)d->width * d->height * 4 * sizeof(float)};
+    }
+};
 
 static int validate_temporal(const lrt_temporal_desc* d, const float* color, const lrt_features* cur,
                              const lrt_temporal_state* prev, const lrt_temporal_state* next, const float* std) {
@@ -253,29 +253,19 @@ static int validate_temporal(const lrt_temporal_desc* d, const float* color, con
         return fail(LRT_E_INVALID, "prev needs color, moment2, normal and world_pos");
     if (int rc = validate_frame_size(d->width, d->height)) return rc;
     if (d->flags != 0 || d->reserved != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
-    if (d->min_history < 1) return fail(LRT_E_INVALID, "min_history must be >= 1");
+    if (int rc = validate_min_history(d->min_history)) return rc;
     for (float v : {d->cur_scale, d->alpha_min, d->normal_min, d->pos_tol, d->short_std})
         if (!std::isfinite(v)) return fail(LRT_E_INVALID, "parameters must be finite");
     if (!(d->cur_scale > 0.0f) || !(d->pos_tol > 0.0f) || !(d->short_std > 0.0f))
         return fail(LRT_E_INVALID, "cur_scale, pos_tol and short_std must be > 0");
-    if (!(d->alpha_min > 0.0f && d->alpha_min <= 1.0f)) return fail(LRT_E_INVALID, "alpha_min must be in (0, 1]");
-    if (!(d->normal_min >= -1.0f && d->normal_min <= 1.0f)) return fail(LRT_E_INVALID, "normal_min must be in [-1, 1]");
+    if (int rc = validate_alpha_min(d->alpha_min)) return rc;
+    if (int rc = validate_normal_min(d->normal_min)) return rc;
     if (int rc = validate_prev_camera(d->prev_camera)) return rc;
     // no output may overlap an input, a prev buffer or another output
-    const size_t bytes = (size_t)d->width * d->height * 4 * sizeof(float);
-    const float* const outs[6] = {next->color, next->moment2, next->normal, next->world_pos, next->albedo, std};
-    const float* const ins[9] = {color, cur->normal, cur->world_pos, cur->albedo,
-                                 prev ? prev->color : nullptr, prev ? prev->moment2 : nullptr,
-                                 prev ? prev->normal : nullptr, prev ? prev->world_pos : nullptr,
-                                 prev ? prev->albedo : nullptr};
-    for (int i = 0; i < 6; ++i) {
-        for (int j = 0; j < 9; ++j)
-            if (ranges_overlap(outs[i], bytes, ins[j], bytes))
-                return fail(LRT_E_INVALID, "aliasing: an output buffer overlaps an input or a prev buffer");
-        for (int j = i + 1; j < 6; ++j)
-            if (ranges_overlap(outs[i], bytes, outs[j], bytes))
-                return fail(LRT_E_INVALID, "aliasing: two output buffers overlap");
-    }
+    TemporalSpans sp(d, color, cur, prev, next, std);
+    if (const int al = spans_alias(sp.v + 9, 6, sp.v, 9))
+        return fail(LRT_E_INVALID, al == 1 ? "aliasing: an output buffer overlaps an input or a prev buffer"
+                                           : "aliasing: two output buffers overlap");
     return LRT_OK;
 }
 
@@ -284,15 +274,9 @@ static int validate_motion(const lrt_temporal_desc* d, const lrt_scene_motion* s
                            const lrt_features* cur, const lrt_temporal_state* prev, const lrt_temporal_state* next,
                            const float* std, const float* motion) {
     if (int rc = validate_scene_motion(sm)) return rc;
-    const size_t bytes = (size_t)d->width * d->height * 4 * sizeof(float);
-    const float* const others[15] = {color, cur->normal, cur->world_pos, cur->albedo,
-                                     prev ? prev->color : nullptr, prev ? prev->moment2 : nullptr,
-                                     prev ? prev->normal : nullptr, prev ? prev->world_pos : nullptr,
-                                     prev ? prev->albedo : nullptr,
-                                     next->color, next->moment2, next->normal, next->world_pos, next->albedo, std};
-    for (const float* o : others)
-        if (ranges_overlap(motion, bytes, o, bytes))
-            return fail(LRT_E_INVALID, "aliasing: motion overlaps another buffer");
+    TemporalSpans sp(d, color, cur, prev, next, std);
+    const Span mo = {motion, sp.v[0].bytes};
+    if (spans_alias(&mo, 1, sp.v, 15)) return fail(LRT_E_INVALID, "aliasing: motion overlaps another buffer");
     return LRT_OK;
 }
 
@@ -360,7 +344,7 @@ static int temporal_device(const lrt_temporal_desc* d, const float* color, const
                            hipStream_t s, const lrt_scene_motion* sm = nullptr, float* motion = nullptr) {
     MotionArgs ma;
     memset(&ma, 0, sizeof(ma));
-    ma.motion = reinterpret_cast<float4*>(motion);
+    ma.motion = quads(motion);
     const bool inl = sm && prev && sm->count <= kInlineSpheres;   // the spheres in the kernel's arguments
     const bool upl = sm && prev && !inl;                         // ... or uploaded to the stream's scratch
     if (upl) {
@@ -370,19 +354,20 @@ static int temporal_device(const lrt_temporal_desc* d, const float* color, const
     }
     TemporalArgs a;
     memset(&a, 0, sizeof(a));
-    auto q = [](const float* p) { return reinterpret_cast<const float4*>(p); };
-    auto qo = [](float* p) { return reinterpret_cast<float4*>(p); };
-    a.color = q(color);
-    a.nrm = q(cur->normal);
-    a.pos = q(cur->world_pos);
-    a.alb = q(cur->albedo);
-    if (prev) a.pc = q(prev->color), a.pm = q(prev->moment2), a.pn = q(prev->normal), a.px = q(prev->world_pos);
-    a.oc = qo(next->color);
-    a.om = qo(next->moment2);
-    a.on = qo(next->normal);
-    a.ox = qo(next->world_pos);
-    a.oa = cur->albedo ? qo(next->albedo) : nullptr;
-    a.ostd = qo(std);
+    a.color = quads(color);
+    a.nrm = quads(cur->normal);
+    a.pos = quads(cur->world_pos);
+    a.alb = quads(cur->albedo);
+    if (prev) {
+        a.pc = quads(prev->color), a.pm = quads(prev->moment2);
+        a.pn = quads(prev->normal), a.px = quads(prev->world_pos);
+    }
+    a.oc = quads(next->color);
+    a.om = quads(next->moment2);
+    a.on = quads(next->normal);
+    a.ox = quads(next->world_pos);
+    a.oa = cur->albedo ? quads(next->albedo) : nullptr;
+    a.ostd = quads(std);
     a.w = d->width;
     a.h = d->height;
     const lrt_camera &c = d->camera, &p = d->prev_camera;
@@ -407,21 +392,21 @@ static int temporal_device(const lrt_temporal_desc* d, const float* color, const
     auto same = [](const lrt_float3& u, const lrt_float3& v) { return !memcmp(&u, &v, sizeof(u)); };
     a.same_cam = same(c.origin, p.origin) && same(c.a, p.a) && same(c.lowerLeftCorner, p.lowerLeftCorner) &&
                  same(c.horizontalVec, p.horizontalVec) && same(c.verticalVec, p.verticalVec);
-    const dim3 grid((unsigned)((a.w + kBlockW - 1) / kBlockW), (unsigned)((a.h + kBlockH - 1) / kBlockH));
+    const dim3 grid = pixel_grid(a.w, a.h);
     if (inl) {
         InlineSpheres sc;
         memset(&sc, 0, sizeof(sc));
         pack_motion(sm, sc.v);
         ma.count = sm->count;
-        temporal_moving_inline_kernel<<<grid, kBlockW * kBlockH, 0, s>>>(a, ma, sc);
+        temporal_moving_inline_kernel<<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a, ma, sc);
     } else if (upl)
-        temporal_moving_kernel<true><<<grid, kBlockW * kBlockH, 0, s>>>(a, ma);
+        temporal_moving_kernel<true><<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a, ma);
     else if (sm)   // nothing to reproject into: motion is (0, 0, -1, 0)
-        temporal_moving_kernel<false><<<grid, kBlockW * kBlockH, 0, s>>>(a, ma);
+        temporal_moving_kernel<false><<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a, ma);
     else if (prev)
-        temporal_kernel<true><<<grid, kBlockW * kBlockH, 0, s>>>(a);
+        temporal_kernel<true><<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a);
     else
-        temporal_kernel<false><<<grid, kBlockW * kBlockH, 0, s>>>(a);
+        temporal_kernel<false><<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a);
     LRT_HIP(hipGetLastError());
     if (upl) LRT_HIP(stream_scratch_used(s));
     return LRT_OK;
@@ -435,10 +420,8 @@ extern "C" {
 
 int lrt_temporal_default(int width, int height, const lrt_camera* camera, const lrt_camera* prev_camera,
                          lrt_temporal_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (!camera) return fail(LRT_E_INVALID, "camera is NULL");
-    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (out && !camera) return fail(LRT_E_INVALID, "camera is NULL");
+    if (int rc = frame_default_begin(out, sizeof(*out), width, height)) return rc;
     out->width = width;
     out->height = height;
     out->min_history = 4;
@@ -470,44 +453,34 @@ static int temporal_host(const lrt_temporal_desc* desc, const float* color, cons
     std::lock_guard<std::mutex> lk(g_mu);
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
-    const size_t bytes = (size_t)desc->width * desc->height * 4 * sizeof(float);
+    const size_t quad = (size_t)desc->width * desc->height * 4 * sizeof(float);
     hipStream_t s = ctx().stream;
-    // Every buffer goes through a device mirror of its own, all in one allocation that lives for
-    // the call: 4 inputs, 4 of the previous state, 6 outputs and the motion frame. The two outputs
-    // whose alpha stays (next->color, color_std) are copied in first.
-    const float* const hin[8] = {color, cur->normal, cur->world_pos, cur->albedo,
-                                 prev ? prev->color : nullptr, prev ? prev->moment2 : nullptr,
-                                 prev ? prev->normal : nullptr, prev ? prev->world_pos : nullptr};
-    float* const hout[6] = {next->color, next->moment2, next->normal, next->world_pos,
-                            cur->albedo ? next->albedo : nullptr, color_std};
-    DeviceStaging<float> m;
-    if (hipMalloc(&m.p, (motion ? 15 : 14) * bytes) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(temporal staging)");
-    const size_t quad = bytes / sizeof(float);
-    float* din[8];
-    float* dout[6];
-    for (int i = 0; i < 8; ++i) {
-        din[i] = hin[i] ? m.p + i * quad : nullptr;
-        if (hin[i]) LRT_HIP(hipMemcpyAsync(din[i], hin[i], bytes, hipMemcpyHostToDevice, s));
-    }
-    for (int i = 0; i < 6; ++i) {
-        dout[i] = hout[i] ? m.p + (8 + i) * quad : nullptr;
-        if (hout[i] && (i == 0 || i == 5)) LRT_HIP(hipMemcpyAsync(dout[i], hout[i], bytes, hipMemcpyHostToDevice, s));
-    }
+    // Every buffer that is given goes through a device mirror of its own. The two outputs whose alpha
+    // stays (next->color, color_std) are copied in first.
+    const lrt_temporal_state none = {};
+    const lrt_temporal_state& p = prev ? *prev : none;
+    HostMirrors m;
+    const int color_ = m.in(color, quad), normal_ = m.in(cur->normal, quad), pos_ = m.in(cur->world_pos, quad);
+    const int albedo_ = m.in(cur->albedo, quad);
+    const int pcolor_ = m.in(p.color, quad), pmoment_ = m.in(p.moment2, quad), pnormal_ = m.in(p.normal, quad);
+    const int ppos_ = m.in(p.world_pos, quad);
+    const int ncolor_ = m.inout(next->color, quad), nmoment_ = m.out(next->moment2, quad);
+    const int nnormal_ = m.out(next->normal, quad), npos_ = m.out(next->world_pos, quad);
+    const int nalbedo_ = m.out(cur->albedo ? next->albedo : nullptr, quad);
+    const int std_ = m.inout(color_std, quad), motion_ = m.out(motion, quad);
+    if (int rc = m.alloc("hipMalloc(temporal staging)")) return rc;
+    if (int rc = m.upload(s)) return rc;
+    auto f = [&m](int i) { return m.dev<float>(i); };
     lrt_features dcur;
     memset(&dcur, 0, sizeof(dcur));
-    dcur.normal = din[1];
-    dcur.world_pos = din[2];
-    dcur.albedo = din[3];
-    const lrt_temporal_state dprev = {din[4], din[5], din[6], din[7], nullptr};
-    const lrt_temporal_state dnext = {dout[0], dout[1], dout[2], dout[3], dout[4]};
-    float* const dmotion = motion ? m.p + 14 * quad : nullptr;
-    if (int rc = temporal_device(desc, din[0], &dcur, prev ? &dprev : nullptr, &dnext, dout[5], s, sm, dmotion))
+    dcur.normal = f(normal_);
+    dcur.world_pos = f(pos_);
+    dcur.albedo = f(albedo_);
+    const lrt_temporal_state dprev = {f(pcolor_), f(pmoment_), f(pnormal_), f(ppos_), nullptr};
+    const lrt_temporal_state dnext = {f(ncolor_), f(nmoment_), f(nnormal_), f(npos_), f(nalbedo_)};
+    if (int rc = temporal_device(desc, f(color_), &dcur, prev ? &dprev : nullptr, &dnext, f(std_), s, sm, f(motion_)))
         return rc;
-    for (int i = 0; i < 6; ++i)
-        if (hout[i]) LRT_HIP(hipMemcpyAsync(hout[i], dout[i], bytes, hipMemcpyDeviceToHost, s));
-    if (motion) LRT_HIP(hipMemcpyAsync(motion, dmotion, bytes, hipMemcpyDeviceToHost, s));
-    LRT_HIP(hipStreamSynchronize(s));
-    return LRT_OK;
+    return m.download(s);
 }
 
 int lrt_temporal_accumulate_host(const lrt_temporal_desc* desc, const float* color, const lrt_features* cur,

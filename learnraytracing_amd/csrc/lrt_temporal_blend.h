@@ -1,10 +1,12 @@
-// Steps 6 and 7 of lrt_temporal_* (include/lrt.h), shared by the pixel functions of lrt_temporal.hip
-// (the static and the moving step) and lrt_temporal_gbuffer.hip (the step driven by the G-buffer's
-// ids and motion vectors). The including unit sets its own contraction. lrt_temporal.hip takes step
-// 7 from here and keeps step 6 in its own text: both choices leave its kernels' instructions what
-// they were before this header existed.
+// Steps 6 and 7 of lrt_temporal_* (include/lrt.h). Step 7 and its store (temporal_std, write_std)
+// serve every kernel that writes color_std: lrt_temporal.hip (the static and the moving step),
+// lrt_temporal_gbuffer.hip, lrt_temporal_upsample.hip and lrt_rectify.hip. Step 6 (temporal_blend)
+// serves lrt_temporal_gbuffer.hip alone: lrt_temporal.hip keeps it in its own text, which leaves its
+// kernels' instructions what they were before this header existed, and
+// lrt_temporal_upsample.hip blends by its own rule. The including unit sets its own contraction.
 #pragma once
 #include "lrt_internal.h"
+#include "lrt_pixel.h"
 
 namespace lrt {
 
@@ -27,6 +29,11 @@ LRT_DEV float3 temporal_std(const float3 col, const float3 m2, const float n, co
         sd = make_float3(sqrtf(fmaxf(m2.x - col.x * col.x, 0.0f)), sqrtf(fmaxf(m2.y - col.y * col.y, 0.0f)),
                          sqrtf(fmaxf(m2.z - col.z * col.z, 0.0f)));
     return sd;
+}
+// ... stored for pixel i where the caller asked for it (12 B: the alpha stays).
+LRT_DEV void write_std(float4* ostd, size_t i, const float3 col, const float3 m2, const float n, const float short_std,
+                       const float min_history) {
+    if (ostd) write_rgb(ostd, i, temporal_std(col, m2, n, short_std, min_history));
 }
 
 }  // namespace lrt

@@ -28,14 +28,10 @@ struct TemporalGbufferArgs {
     float k, alpha_min, normal_min, short_std, min_history;
 };
 
-// lrt_temporal.hip's shape: a wave covers 8 x 8 pixels, a workgroup of four waves 32 x 8.
-constexpr int kBlockW = 32, kBlockH = 8;
-
 // One pixel of the step. kHist: there is a previous state (else every pixel is reset).
 template <bool kHist>
-__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_gbuffer_kernel(TemporalGbufferArgs a) {
-    const int t = threadIdx.x;   // wave t / 64, its lane's pixel (t % 8, t / 8 % 8)
-    const int x = blockIdx.x * kBlockW + (t >> 6) * 8 + (t & 7), y = blockIdx.y * kBlockH + ((t >> 3) & 7);
+__global__ __launch_bounds__(kPixBlockW* kPixBlockH) void temporal_gbuffer_kernel(TemporalGbufferArgs a) {
+    const int x = block_x(), y = block_y();
     if (x >= a.w || y >= a.h) return;
     const size_t ip = (size_t)y * a.w + x;
     const float4 c4 = a.color[ip];
@@ -81,18 +77,9 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_gbuffer_kernel(Temp
         }
         if (sw > 1e-3f) temporal_blend(sw, sn, sc, sm, C, a.alpha_min, col, m2, n);
     }
-    float* const oc = reinterpret_cast<float*>(a.oc + ip);   // 12 B: the alpha stays
-    oc[0] = col.x;
-    oc[1] = col.y;
-    oc[2] = col.z;
+    write_rgb(a.oc, ip, col);
     a.om[ip] = make_float4(m2.x, m2.y, m2.z, n);
-    if (a.ostd) {
-        const float3 sd = temporal_std(col, m2, n, a.short_std, a.min_history);
-        float* const os = reinterpret_cast<float*>(a.ostd + ip);
-        os[0] = sd.x;
-        os[1] = sd.y;
-        os[2] = sd.z;
-    }
+    write_std(a.ostd, ip, col, m2, n, a.short_std, a.min_history);
 }
 
 // Everything that needs neither the library's state nor the device.
@@ -103,17 +90,15 @@ static int validate_temporal_gbuffer(const lrt_temporal_gbuffer_desc* d, const f
     if (!color) return fail(LRT_E_INVALID, "color is NULL");
     if (!cur || !cur->normal || !cur->motion || !cur->id) return fail(LRT_E_INVALID, "cur needs normal, motion and id");
     if (!next || !next->color || !next->moment2) return fail(LRT_E_INVALID, "next needs color and moment2");
-    if (!prev != !prev_g) return fail(LRT_E_INVALID, "prev and prev_g must both be given, or neither");
-    if (prev && (!prev->color || !prev->moment2)) return fail(LRT_E_INVALID, "prev needs color and moment2");
-    if (prev_g && (!prev_g->normal || !prev_g->id)) return fail(LRT_E_INVALID, "prev_g needs normal and id");
+    if (int rc = validate_history_pair(prev, prev_g)) return rc;
     if (int rc = validate_frame_size(d->width, d->height)) return rc;
     if (d->flags != 0 || d->reserved != 0 || d->reserved2 != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
-    if (d->min_history < 1) return fail(LRT_E_INVALID, "min_history must be >= 1");
+    if (int rc = validate_min_history(d->min_history)) return rc;
     for (float v : {d->cur_scale, d->alpha_min, d->normal_min, d->short_std})
         if (!std::isfinite(v)) return fail(LRT_E_INVALID, "parameters must be finite");
     if (!(d->cur_scale > 0.0f) || !(d->short_std > 0.0f)) return fail(LRT_E_INVALID, "cur_scale and short_std must be > 0");
-    if (!(d->alpha_min > 0.0f && d->alpha_min <= 1.0f)) return fail(LRT_E_INVALID, "alpha_min must be in (0, 1]");
-    if (!(d->normal_min >= -1.0f && d->normal_min <= 1.0f)) return fail(LRT_E_INVALID, "normal_min must be in [-1, 1]");
+    if (int rc = validate_alpha_min(d->alpha_min)) return rc;
+    if (int rc = validate_normal_min(d->normal_min)) return rc;
     // no output may overlap an input, a previous buffer or another output
     const size_t px = (size_t)d->width * d->height, quad = 16 * px, word = 4 * px;
     const Span outs[3] = {{next->color, quad}, {next->moment2, quad}, {std, quad}};
@@ -123,13 +108,7 @@ static int validate_temporal_gbuffer(const lrt_temporal_gbuffer_desc* d, const f
     if (const int al = spans_alias(outs, 3, ins, 8))
         return fail(LRT_E_INVALID, al == 1 ? "aliasing: an output buffer overlaps an input or a prev buffer"
                                            : "aliasing: two output buffers overlap");
-    // a G-buffer overwritten in place is no history
-    if (prev_g)
-        for (const Span& c : {ins[1], ins[3]})
-            for (const Span& p : {ins[6], ins[7]})
-                if (ranges_overlap(c.p, c.bytes, p.p, p.bytes))
-                    return fail(LRT_E_INVALID, "aliasing: cur's normal or id overlaps prev_g's");
-    return LRT_OK;
+    return validate_gbuffer_kept(ins[1], ins[3], ins[6], ins[7]);
 }
 
 // The step on stream s (device pointers, validated).
@@ -138,15 +117,14 @@ static int temporal_gbuffer_device(const lrt_temporal_gbuffer_desc* d, const flo
                                    const lrt_temporal_state* next, float* std, hipStream_t s) {
     TemporalGbufferArgs a;
     memset(&a, 0, sizeof(a));
-    auto q = [](const float* p) { return reinterpret_cast<const float4*>(p); };
-    a.color = q(color);
-    a.nrm = q(cur->normal);
-    a.motion = q(cur->motion);
+    a.color = quads(color);
+    a.nrm = quads(cur->normal);
+    a.motion = quads(cur->motion);
     a.id = cur->id;
-    if (prev) a.pc = q(prev->color), a.pm = q(prev->moment2), a.pn = q(prev_g->normal), a.pid = prev_g->id;
-    a.oc = reinterpret_cast<float4*>(next->color);
-    a.om = reinterpret_cast<float4*>(next->moment2);
-    a.ostd = reinterpret_cast<float4*>(std);
+    if (prev) a.pc = quads(prev->color), a.pm = quads(prev->moment2), a.pn = quads(prev_g->normal), a.pid = prev_g->id;
+    a.oc = quads(next->color);
+    a.om = quads(next->moment2);
+    a.ostd = quads(std);
     a.w = d->width;
     a.h = d->height;
     a.k = d->cur_scale;
@@ -154,11 +132,11 @@ static int temporal_gbuffer_device(const lrt_temporal_gbuffer_desc* d, const flo
     a.normal_min = d->normal_min;
     a.short_std = d->short_std;
     a.min_history = (float)d->min_history;
-    const dim3 grid((unsigned)((a.w + kBlockW - 1) / kBlockW), (unsigned)((a.h + kBlockH - 1) / kBlockH));
+    const dim3 grid = pixel_grid(a.w, a.h);
     if (prev)
-        temporal_gbuffer_kernel<true><<<grid, kBlockW * kBlockH, 0, s>>>(a);
+        temporal_gbuffer_kernel<true><<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a);
     else
-        temporal_gbuffer_kernel<false><<<grid, kBlockW * kBlockH, 0, s>>>(a);
+        temporal_gbuffer_kernel<false><<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a);
     LRT_HIP(hipGetLastError());
     return LRT_OK;
 }
@@ -170,9 +148,7 @@ using namespace lrt;
 extern "C" {
 
 int lrt_temporal_gbuffer_default(int width, int height, lrt_temporal_gbuffer_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (int rc = frame_default_begin(out, sizeof(*out), width, height)) return rc;
     out->width = width;
     out->height = height;
     out->min_history = 4;
@@ -205,48 +181,32 @@ int lrt_temporal_accumulate_gbuffer_host(const lrt_temporal_gbuffer_desc* desc, 
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     hipStream_t s = ctx().stream;
-    // Every buffer goes through a device mirror of its own, all in one allocation that lives for the
-    // call: nine RGBA frames (3 inputs, 3 of the history, 3 outputs), then the two id planes, so that
-    // every mirror stays 16 B aligned. The two outputs whose alpha stays are copied in first.
+    // Every buffer that is given goes through a device mirror of its own. The two outputs whose alpha
+    // stays (next->color, color_std) are copied in first.
     const size_t px = (size_t)desc->width * desc->height, quad = 16 * px, word = 4 * px;
-    const float* const hin[6] = {color, cur->normal, cur->motion, prev ? prev->color : nullptr,
-                                 prev ? prev->moment2 : nullptr, prev_g ? prev_g->normal : nullptr};
-    const int32_t* const hid[2] = {cur->id, prev_g ? prev_g->id : nullptr};
-    float* const hout[3] = {next->color, next->moment2, color_std};
-    DeviceStaging<char> m;
-    if (hipMalloc(&m.p, 9 * quad + 2 * word) != hipSuccess) return fail(LRT_E_NOMEM, "hipMalloc(temporal staging)");
-    float* din[6];
-    float* dout[3];
-    int32_t* did[2];
-    for (int i = 0; i < 6; ++i) {
-        din[i] = hin[i] ? reinterpret_cast<float*>(m.p + i * quad) : nullptr;
-        if (hin[i]) LRT_HIP(hipMemcpyAsync(din[i], hin[i], quad, hipMemcpyHostToDevice, s));
-    }
-    for (int i = 0; i < 2; ++i) {
-        did[i] = hid[i] ? reinterpret_cast<int32_t*>(m.p + 9 * quad + i * word) : nullptr;
-        if (hid[i]) LRT_HIP(hipMemcpyAsync(did[i], hid[i], word, hipMemcpyHostToDevice, s));
-    }
-    for (int i = 0; i < 3; ++i) {
-        dout[i] = hout[i] ? reinterpret_cast<float*>(m.p + (6 + i) * quad) : nullptr;
-        if (hout[i] && i != 1) LRT_HIP(hipMemcpyAsync(dout[i], hout[i], quad, hipMemcpyHostToDevice, s));
-    }
+    HostMirrors m;
+    const int color_ = m.in(color, quad), normal_ = m.in(cur->normal, quad), motion_ = m.in(cur->motion, quad);
+    const int id_ = m.in(cur->id, word);
+    const int pcolor_ = m.in(prev ? prev->color : nullptr, quad), pmoment_ = m.in(prev ? prev->moment2 : nullptr, quad);
+    const int pnormal_ = m.in(prev_g ? prev_g->normal : nullptr, quad), pid_ = m.in(prev_g ? prev_g->id : nullptr, word);
+    const int ncolor_ = m.inout(next->color, quad), nmoment_ = m.out(next->moment2, quad), std_ = m.inout(color_std, quad);
+    if (int rc = m.alloc("hipMalloc(temporal staging)")) return rc;
+    if (int rc = m.upload(s)) return rc;
+    auto f = [&m](int i) { return m.dev<float>(i); };
     lrt_gbuffer dcur, dprev_g;
     memset(&dcur, 0, sizeof(dcur));
     memset(&dprev_g, 0, sizeof(dprev_g));
-    dcur.normal = din[1];
-    dcur.motion = din[2];
-    dcur.id = did[0];
-    dprev_g.normal = din[5];
-    dprev_g.id = did[1];
-    const lrt_temporal_state dprev = {din[3], din[4], nullptr, nullptr, nullptr};
-    const lrt_temporal_state dnext = {dout[0], dout[1], nullptr, nullptr, nullptr};
-    if (int rc = temporal_gbuffer_device(desc, din[0], &dcur, prev ? &dprev_g : nullptr, prev ? &dprev : nullptr, &dnext,
-                                         dout[2], s))
+    dcur.normal = f(normal_);
+    dcur.motion = f(motion_);
+    dcur.id = m.dev<int32_t>(id_);
+    dprev_g.normal = f(pnormal_);
+    dprev_g.id = m.dev<int32_t>(pid_);
+    const lrt_temporal_state dprev = {f(pcolor_), f(pmoment_), nullptr, nullptr, nullptr};
+    const lrt_temporal_state dnext = {f(ncolor_), f(nmoment_), nullptr, nullptr, nullptr};
+    if (int rc = temporal_gbuffer_device(desc, f(color_), &dcur, prev ? &dprev_g : nullptr, prev ? &dprev : nullptr, &dnext,
+                                         f(std_), s))
         return rc;
-    for (int i = 0; i < 3; ++i)
-        if (hout[i]) LRT_HIP(hipMemcpyAsync(hout[i], dout[i], quad, hipMemcpyDeviceToHost, s));
-    LRT_HIP(hipStreamSynchronize(s));
-    return LRT_OK;
+    return m.download(s);
 }
 
 }  // extern "C"

@@ -37,8 +37,6 @@ struct TemporalUpsampleArgs {
     float weight_min, alpha_min, normal_min, short_std, min_history;
 };
 
-// lrt_temporal.hip's shape: a wave covers 8 x 8 pixels, a workgroup of four waves 32 x 8.
-constexpr int kBlockW = 32, kBlockH = 8;
 constexpr int kMaxSize = 32768;   // (2x + 1) low_width + width stays below 2^31
 
 // Step 1 along one axis: the first tap and the weight of the second, for output coordinate x of n
@@ -62,9 +60,8 @@ __device__ __forceinline__ float3 add_tap(const float3 s, bool on, float w, cons
 
 // One pixel of the step. kHist: there is a previous state (else classes 2 and 3 only).
 template <bool kHist>
-__global__ __launch_bounds__(kBlockW* kBlockH) void temporal_upsample_kernel(TemporalUpsampleArgs a) {
-    const int t = threadIdx.x;   // wave t / 64, its lane's pixel (t % 8, t / 8 % 8)
-    const int x = blockIdx.x * kBlockW + (t >> 6) * 8 + (t & 7), y = blockIdx.y * kBlockH + ((t >> 3) & 7);
+__global__ __launch_bounds__(kPixBlockW* kPixBlockH) void temporal_upsample_kernel(TemporalUpsampleArgs a) {
+    const int x = block_x(), y = block_y();
     if (x >= a.w || y >= a.h) return;
     const size_t ip = (size_t)y * a.w + x;
     int lx0, ly0;
@@ -189,18 +186,9 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void temporal_upsample_kernel(Tem
         m2 = make_float3(col.x * col.x, col.y * col.y, col.z * col.z);
         n = 0.0f;
     }
-    float* const oc = reinterpret_cast<float*>(a.oc + ip);   // 12 B: the alpha stays
-    oc[0] = col.x;
-    oc[1] = col.y;
-    oc[2] = col.z;
+    write_rgb(a.oc, ip, col);
     a.om[ip] = make_float4(m2.x, m2.y, m2.z, n);
-    if (a.ostd) {
-        const float3 sd = temporal_std(col, m2, n, a.short_std, a.min_history);
-        float* const os = reinterpret_cast<float*>(a.ostd + ip);
-        os[0] = sd.x;
-        os[1] = sd.y;
-        os[2] = sd.z;
-    }
+    write_std(a.ostd, ip, col, m2, n, a.short_std, a.min_history);
     if (a.cls) a.cls[ip] = cls;
 }
 
@@ -224,21 +212,19 @@ static int validate_temporal_upsample(const lrt_temporal_upsample_desc* d, const
     if (!low || !low->id || !low->normal) return fail(LRT_E_INVALID, "low needs id and normal");
     if (!cur || !cur->normal || !cur->motion || !cur->id) return fail(LRT_E_INVALID, "cur needs normal, motion and id");
     if (!next || !next->color || !next->moment2) return fail(LRT_E_INVALID, "next needs color and moment2");
-    if (!prev != !prev_g) return fail(LRT_E_INVALID, "prev and prev_g must both be given, or neither");
-    if (prev && (!prev->color || !prev->moment2)) return fail(LRT_E_INVALID, "prev needs color and moment2");
-    if (prev_g && (!prev_g->normal || !prev_g->id)) return fail(LRT_E_INVALID, "prev_g needs normal and id");
+    if (int rc = validate_history_pair(prev, prev_g)) return rc;
     if (int rc = validate_sizes_and_jitter(d->width, d->height, d->low_width, d->low_height, d->jitter_x, d->jitter_y))
         return rc;
     if (d->flags != 0 || d->reserved != 0) return fail(LRT_E_INVALID, "flags and reserved must be 0");
-    if (d->min_history < 1) return fail(LRT_E_INVALID, "min_history must be >= 1");
+    if (int rc = validate_min_history(d->min_history)) return rc;
     for (float v : {d->cur_scale, d->alpha_min, d->normal_min, d->short_std, d->sigma_normal, d->sigma_sample,
                     d->weight_min})
         if (!std::isfinite(v)) return fail(LRT_E_INVALID, "parameters must be finite");
     for (float v : {d->cur_scale, d->short_std, d->sigma_normal, d->sigma_sample, d->weight_min})
         if (!(v > 0.0f))
             return fail(LRT_E_INVALID, "cur_scale, short_std, sigma_normal, sigma_sample and weight_min must be > 0");
-    if (!(d->alpha_min > 0.0f && d->alpha_min <= 1.0f)) return fail(LRT_E_INVALID, "alpha_min must be in (0, 1]");
-    if (!(d->normal_min >= -1.0f && d->normal_min <= 1.0f)) return fail(LRT_E_INVALID, "normal_min must be in [-1, 1]");
+    if (int rc = validate_alpha_min(d->alpha_min)) return rc;
+    if (int rc = validate_normal_min(d->normal_min)) return rc;
     // no output may overlap an input, a previous buffer or another output
     const size_t px = (size_t)d->width * d->height, lpx = (size_t)d->low_width * d->low_height;
     const size_t quad = 16 * px, word = 4 * px;
@@ -250,13 +236,7 @@ static int validate_temporal_upsample(const lrt_temporal_upsample_desc* d, const
     if (const int al = spans_alias(outs, 4, ins, 10))
         return fail(LRT_E_INVALID, al == 1 ? "aliasing: an output buffer overlaps an input or a prev buffer"
                                            : "aliasing: two output buffers overlap");
-    // a G-buffer overwritten in place is no history
-    if (prev_g)
-        for (const Span& c : {ins[0], ins[1]})
-            for (const Span& p : {ins[3], ins[4]})
-                if (ranges_overlap(c.p, c.bytes, p.p, p.bytes))
-                    return fail(LRT_E_INVALID, "aliasing: cur's normal or id overlaps prev_g's");
-    return LRT_OK;
+    return validate_gbuffer_kept(ins[0], ins[1], ins[3], ins[4]);
 }
 
 // The step on stream s (device pointers, validated).
@@ -265,17 +245,16 @@ static int temporal_upsample_device(const lrt_temporal_upsample_desc* d, const f
                                     const lrt_temporal_state* next, float* std, int32_t* cls, hipStream_t s) {
     TemporalUpsampleArgs a;
     memset(&a, 0, sizeof(a));
-    auto q = [](const float* p) { return reinterpret_cast<const float4*>(p); };
-    a.color = q(color_low);
-    a.ln = q(low->normal);
+    a.color = quads(color_low);
+    a.ln = quads(low->normal);
     a.lid = low->id;
-    a.nrm = q(cur->normal);
-    a.motion = q(cur->motion);
+    a.nrm = quads(cur->normal);
+    a.motion = quads(cur->motion);
     a.id = cur->id;
-    if (prev) a.pc = q(prev->color), a.pm = q(prev->moment2), a.pn = q(prev_g->normal), a.pid = prev_g->id;
-    a.oc = reinterpret_cast<float4*>(next->color);
-    a.om = reinterpret_cast<float4*>(next->moment2);
-    a.ostd = reinterpret_cast<float4*>(std);
+    if (prev) a.pc = quads(prev->color), a.pm = quads(prev->moment2), a.pn = quads(prev_g->normal), a.pid = prev_g->id;
+    a.oc = quads(next->color);
+    a.om = quads(next->moment2);
+    a.ostd = quads(std);
     a.cls = cls;
     a.w = d->width;
     a.h = d->height;
@@ -293,11 +272,11 @@ static int temporal_upsample_device(const lrt_temporal_upsample_desc* d, const f
     a.normal_min = d->normal_min;
     a.short_std = d->short_std;
     a.min_history = (float)d->min_history;
-    const dim3 grid((unsigned)((a.w + kBlockW - 1) / kBlockW), (unsigned)((a.h + kBlockH - 1) / kBlockH));
+    const dim3 grid = pixel_grid(a.w, a.h);
     if (prev)
-        temporal_upsample_kernel<true><<<grid, kBlockW * kBlockH, 0, s>>>(a);
+        temporal_upsample_kernel<true><<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a);
     else
-        temporal_upsample_kernel<false><<<grid, kBlockW * kBlockH, 0, s>>>(a);
+        temporal_upsample_kernel<false><<<grid, kPixBlockW * kPixBlockH, 0, s>>>(a);
     LRT_HIP(hipGetLastError());
     return LRT_OK;
 }
@@ -309,9 +288,8 @@ using namespace lrt;
 extern "C" {
 
 int lrt_temporal_upsample_default(int width, int height, int low_width, int low_height, lrt_temporal_upsample_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (width < 1 || height < 1 || low_width < 1 || low_height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (int rc = frame_default_begin(out, sizeof(*out), std::min(width, low_width), std::min(height, low_height)))
+        return rc;
     out->width = width;
     out->height = height;
     out->low_width = low_width;
@@ -365,62 +343,37 @@ int lrt_temporal_upsample_host(const lrt_temporal_upsample_desc* desc, const flo
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     hipStream_t s = ctx().stream;
-    // Every buffer goes through a device mirror of its own, all in one allocation that lives for the
-    // call: eight RGBA frames of the output size (2 of cur, 3 of the history, 3 outputs), two of the
-    // low size, then the three id planes and the class plane, so that every RGBA mirror stays 16 B
-    // aligned. The two outputs whose alpha stays are copied in first.
+    // Every buffer that is given goes through a device mirror of its own. The two outputs whose alpha
+    // stays (next->color, color_std) are copied in first.
     const size_t px = (size_t)desc->width * desc->height, lpx = (size_t)desc->low_width * desc->low_height;
     const size_t quad = 16 * px, word = 4 * px, lquad = 16 * lpx, lword = 4 * lpx;
-    const float* const hin[5] = {cur->normal, cur->motion, prev ? prev->color : nullptr, prev ? prev->moment2 : nullptr,
-                                 prev_g ? prev_g->normal : nullptr};
-    float* const hout[3] = {next->color, next->moment2, color_std};
-    DeviceStaging<char> m;
-    if (hipMalloc(&m.p, 8 * quad + 2 * lquad + 3 * word + lword) != hipSuccess)
-        return fail(LRT_E_NOMEM, "hipMalloc(temporal upsample staging)");
-    float* din[5];
-    float* dout[3];
-    for (int i = 0; i < 5; ++i) {
-        din[i] = hin[i] ? reinterpret_cast<float*>(m.p + i * quad) : nullptr;
-        if (hin[i]) LRT_HIP(hipMemcpyAsync(din[i], hin[i], quad, hipMemcpyHostToDevice, s));
-    }
-    for (int i = 0; i < 3; ++i) {
-        dout[i] = hout[i] ? reinterpret_cast<float*>(m.p + (5 + i) * quad) : nullptr;
-        if (hout[i] && i != 1) LRT_HIP(hipMemcpyAsync(dout[i], hout[i], quad, hipMemcpyHostToDevice, s));
-    }
-    char* const lows = m.p + 8 * quad;
-    float* const dcolor = reinterpret_cast<float*>(lows);
-    float* const dlnormal = reinterpret_cast<float*>(lows + lquad);
-    char* const words = lows + 2 * lquad;
-    int32_t* const dcid = reinterpret_cast<int32_t*>(words);
-    int32_t* const dpid = prev_g ? reinterpret_cast<int32_t*>(words + word) : nullptr;
-    int32_t* const dcls = class_out ? reinterpret_cast<int32_t*>(words + 2 * word) : nullptr;
-    int32_t* const dlid = reinterpret_cast<int32_t*>(words + 3 * word);
-    LRT_HIP(hipMemcpyAsync(dcolor, color_low, lquad, hipMemcpyHostToDevice, s));
-    LRT_HIP(hipMemcpyAsync(dlnormal, low->normal, lquad, hipMemcpyHostToDevice, s));
-    LRT_HIP(hipMemcpyAsync(dcid, cur->id, word, hipMemcpyHostToDevice, s));
-    if (prev_g) LRT_HIP(hipMemcpyAsync(dpid, prev_g->id, word, hipMemcpyHostToDevice, s));
-    LRT_HIP(hipMemcpyAsync(dlid, low->id, lword, hipMemcpyHostToDevice, s));
+    HostMirrors m;
+    const int color_ = m.in(color_low, lquad), lnormal_ = m.in(low->normal, lquad), lid_ = m.in(low->id, lword);
+    const int normal_ = m.in(cur->normal, quad), motion_ = m.in(cur->motion, quad), id_ = m.in(cur->id, word);
+    const int pcolor_ = m.in(prev ? prev->color : nullptr, quad), pmoment_ = m.in(prev ? prev->moment2 : nullptr, quad);
+    const int pnormal_ = m.in(prev_g ? prev_g->normal : nullptr, quad), pid_ = m.in(prev_g ? prev_g->id : nullptr, word);
+    const int ncolor_ = m.inout(next->color, quad), nmoment_ = m.out(next->moment2, quad), std_ = m.inout(color_std, quad);
+    const int class_ = m.out(class_out, word);
+    if (int rc = m.alloc("hipMalloc(temporal upsample staging)")) return rc;
+    if (int rc = m.upload(s)) return rc;
+    auto f = [&m](int i) { return m.dev<float>(i); };
     lrt_gbuffer dlow, dcur, dprev_g;
     memset(&dlow, 0, sizeof(dlow));
     memset(&dcur, 0, sizeof(dcur));
     memset(&dprev_g, 0, sizeof(dprev_g));
-    dlow.normal = dlnormal;
-    dlow.id = dlid;
-    dcur.normal = din[0];
-    dcur.motion = din[1];
-    dcur.id = dcid;
-    dprev_g.normal = din[4];
-    dprev_g.id = dpid;
-    const lrt_temporal_state dprev = {din[2], din[3], nullptr, nullptr, nullptr};
-    const lrt_temporal_state dnext = {dout[0], dout[1], nullptr, nullptr, nullptr};
-    if (int rc = temporal_upsample_device(desc, dcolor, &dlow, &dcur, prev ? &dprev_g : nullptr, prev ? &dprev : nullptr,
-                                          &dnext, dout[2], dcls, s))
+    dlow.normal = f(lnormal_);
+    dlow.id = m.dev<int32_t>(lid_);
+    dcur.normal = f(normal_);
+    dcur.motion = f(motion_);
+    dcur.id = m.dev<int32_t>(id_);
+    dprev_g.normal = f(pnormal_);
+    dprev_g.id = m.dev<int32_t>(pid_);
+    const lrt_temporal_state dprev = {f(pcolor_), f(pmoment_), nullptr, nullptr, nullptr};
+    const lrt_temporal_state dnext = {f(ncolor_), f(nmoment_), nullptr, nullptr, nullptr};
+    if (int rc = temporal_upsample_device(desc, f(color_), &dlow, &dcur, prev ? &dprev_g : nullptr, prev ? &dprev : nullptr,
+                                          &dnext, f(std_), m.dev<int32_t>(class_), s))
         return rc;
-    for (int i = 0; i < 3; ++i)
-        if (hout[i]) LRT_HIP(hipMemcpyAsync(hout[i], dout[i], quad, hipMemcpyDeviceToHost, s));
-    if (class_out) LRT_HIP(hipMemcpyAsync(class_out, dcls, word, hipMemcpyDeviceToHost, s));
-    LRT_HIP(hipStreamSynchronize(s));
-    return LRT_OK;
+    return m.download(s);
 }
 
 }  // extern "C"

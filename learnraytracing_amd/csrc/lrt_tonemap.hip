@@ -230,7 +230,7 @@ static int tonemap_device(const lrt_tonemap_desc* d, const float* color, lrt_exp
             total = static_cast<uint32_t*>(p);
         }
         LRT_HIP(hipMemsetAsync(total, 0, kWords * sizeof(uint32_t), s));
-        meter_kernel<<<groups, kMeterBlock, 0, s>>>(reinterpret_cast<const float4*>(color), npix, total);
+        meter_kernel<<<groups, kMeterBlock, 0, s>>>(quads(color), npix, total);
         LRT_HIP(hipGetLastError());
         ExposureArgs x;
         memset(&x, 0, sizeof(x));
@@ -251,8 +251,8 @@ static int tonemap_device(const lrt_tonemap_desc* d, const float* color, lrt_exp
     if (out || bgra) {
         MapArgs m;
         memset(&m, 0, sizeof(m));
-        m.color = reinterpret_cast<const float4*>(color);
-        m.out = reinterpret_cast<float4*>(out);
+        m.color = quads(color);
+        m.out = quads(out);
         m.bgra = bgra;
         m.state = d->auto_exposure ? state : nullptr;
         m.ev = d->ev_bias;
@@ -272,9 +272,7 @@ using namespace lrt;
 extern "C" {
 
 int lrt_tonemap_default(int width, int height, lrt_tonemap_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (width < 1 || height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (int rc = frame_default_begin(out, sizeof(*out), width, height)) return rc;
     out->width = width;
     out->height = height;
     out->op = LRT_TM_ACES;
@@ -308,36 +306,21 @@ int lrt_tonemap_host(const lrt_tonemap_desc* desc, const float* color, lrt_expos
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     const size_t npix = (size_t)desc->width * desc->height;
-    const size_t frame = npix * 4 * sizeof(float), words = kWords * sizeof(uint32_t);
-    const bool meter = desc->auto_exposure != 0;
+    const bool meter = desc->auto_exposure != 0, in_place = out == color;
     hipStream_t s = ctx().stream;
-    // Device mirrors in one allocation that lives for the call: color, out (copied in first: its
-    // alpha stays; in place it is color's mirror), bgra, then the histogram and the state, which
-    // are mirrored only when the call meters.
-    DeviceStaging<char> m;
-    if (hipMalloc(&m.p, 2 * frame + npix * sizeof(uint32_t) + words + sizeof(lrt_exposure_state)) != hipSuccess)
-        return fail(LRT_E_NOMEM, "hipMalloc(tonemap staging)");
-    float* const d_color = reinterpret_cast<float*>(m.p);
-    float* d_out = nullptr;
-    uint32_t* const d_bgra = bgra ? reinterpret_cast<uint32_t*>(m.p + 2 * frame) : nullptr;
-    uint32_t* const d_hist = meter && histogram ? reinterpret_cast<uint32_t*>(m.p + 2 * frame + npix * 4) : nullptr;
-    lrt_exposure_state* const d_state =
-        meter ? reinterpret_cast<lrt_exposure_state*>(m.p + 2 * frame + npix * 4 + words) : nullptr;
-    LRT_HIP(hipMemcpyAsync(d_color, color, frame, hipMemcpyHostToDevice, s));
-    if (out == color) {
-        d_out = d_color;
-    } else if (out) {
-        d_out = reinterpret_cast<float*>(m.p + frame);
-        LRT_HIP(hipMemcpyAsync(d_out, out, frame, hipMemcpyHostToDevice, s));
-    }
-    if (d_state) LRT_HIP(hipMemcpyAsync(d_state, state, sizeof(*state), hipMemcpyHostToDevice, s));
-    if (int rc = tonemap_device(desc, d_color, d_state, d_hist, d_out, d_bgra, s)) return rc;
-    if (out) LRT_HIP(hipMemcpyAsync(out, d_out, frame, hipMemcpyDeviceToHost, s));
-    if (bgra) LRT_HIP(hipMemcpyAsync(bgra, d_bgra, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (d_hist) LRT_HIP(hipMemcpyAsync(histogram, d_hist, words, hipMemcpyDeviceToHost, s));
-    if (d_state) LRT_HIP(hipMemcpyAsync(state, d_state, sizeof(*state), hipMemcpyDeviceToHost, s));
-    LRT_HIP(hipStreamSynchronize(s));
-    return LRT_OK;
+    // Device mirrors: color, out (copied in first: its alpha stays; in place it is color's mirror),
+    // bgra, and the histogram and the state, which are mirrored only when the call meters.
+    HostMirrors m;
+    const int color_ = m.add(color, in_place ? out : nullptr, npix * 16);
+    const int out_ = in_place ? color_ : m.inout(out, npix * 16), bgra_ = m.out(bgra, npix * 4);
+    const int hist_ = m.out(meter ? histogram : nullptr, kWords * sizeof(uint32_t));
+    const int state_ = m.inout(meter ? state : nullptr, sizeof(lrt_exposure_state));
+    if (int rc = m.alloc("hipMalloc(tonemap staging)")) return rc;
+    if (int rc = m.upload(s)) return rc;
+    if (int rc = tonemap_device(desc, m.dev<float>(color_), m.dev<lrt_exposure_state>(state_), m.dev<uint32_t>(hist_),
+                                m.dev<float>(out_), m.dev<uint32_t>(bgra_), s))
+        return rc;
+    return m.download(s);
 }
 
 }  // extern "C"

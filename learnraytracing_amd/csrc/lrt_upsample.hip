@@ -6,6 +6,7 @@
 // albedo. One launch, no atomics, no LDS, no barrier. No id is used as an index. Not bit-pinned:
 // contraction is allowed, as in the temporal units.
 #include "lrt_internal.h"
+#include "lrt_pixel.h"
 
 #pragma clang fp contract(fast)
 
@@ -26,8 +27,6 @@ struct UpsampleArgs {
     float floor_a, weight_min;
 };
 
-// lrt_temporal.hip's shape: a wave covers 8 x 8 pixels, a workgroup of four waves 32 x 8.
-constexpr int kBlockW = 32, kBlockH = 8;
 constexpr int kMaxSize = 32768;   // (2x + 1) low_width stays below 2^31
 
 // Step 1 along one axis: the first tap and the weight of the second, for output coordinate x of n
@@ -71,9 +70,8 @@ __device__ __forceinline__ float normal_weight(const float4 nq, const float4 np,
 // One pixel. kBilinear: LRT_UP_BILINEAR (every pixel is class 2, no normal is read); kAlbedo: both
 // albedo planes are given.
 template <bool kBilinear, bool kAlbedo>
-__global__ __launch_bounds__(kBlockW* kBlockH) void upsample_kernel(UpsampleArgs a) {
-    const int t = threadIdx.x;   // wave t / 64, its lane's pixel (t % 8, t / 8 % 8)
-    const int x = blockIdx.x * kBlockW + (t >> 6) * 8 + (t & 7), y = blockIdx.y * kBlockH + ((t >> 3) & 7);
+__global__ __launch_bounds__(kPixBlockW* kPixBlockH) void upsample_kernel(UpsampleArgs a) {
+    const int x = block_x(), y = block_y();
     if (x >= a.w || y >= a.h) return;
     const size_t ip = (size_t)y * a.w + x;
     int x0, y0;
@@ -156,10 +154,7 @@ __global__ __launch_bounds__(kBlockW* kBlockH) void upsample_kernel(UpsampleArgs
     }
     if (kAlbedo && id >= 0)
         I = make_float3(I.x * fmaxf(ah.x, a.floor_a), I.y * fmaxf(ah.y, a.floor_a), I.z * fmaxf(ah.z, a.floor_a));
-    float* const o = reinterpret_cast<float*>(a.out + ip);   // 12 B: the alpha stays
-    o[0] = I.x;
-    o[1] = I.y;
-    o[2] = I.z;
+    write_rgb(a.out, ip, I);
     if (a.cls) a.cls[ip] = cls;
 }
 
@@ -200,16 +195,15 @@ static int upsample_device(const lrt_upsample_desc* d, const float* color_low, c
                            const lrt_gbuffer* high, float* out, int32_t* cls, hipStream_t s) {
     UpsampleArgs a;
     memset(&a, 0, sizeof(a));
-    auto q = [](const float* p) { return reinterpret_cast<const float4*>(p); };
     const bool bilinear = (d->flags & LRT_UP_BILINEAR) != 0, albedo = low->albedo != nullptr;
-    a.color = q(color_low);
-    a.ln = bilinear ? nullptr : q(low->normal);
-    a.la = q(low->albedo);
+    a.color = quads(color_low);
+    a.ln = bilinear ? nullptr : quads(low->normal);
+    a.la = quads(low->albedo);
     a.lid = low->id;
-    a.hn = bilinear ? nullptr : q(high->normal);
-    a.ha = q(high->albedo);
+    a.hn = bilinear ? nullptr : quads(high->normal);
+    a.ha = quads(high->albedo);
     a.hid = high->id;
-    a.out = reinterpret_cast<float4*>(out);
+    a.out = quads(out);
     a.cls = cls;
     a.w = d->width;
     a.h = d->height;
@@ -218,8 +212,8 @@ static int upsample_device(const lrt_upsample_desc* d, const float* color_low, c
     a.kn = -1.44269504f / (d->sigma_normal * d->sigma_normal);
     a.floor_a = d->albedo_floor;
     a.weight_min = d->weight_min;
-    const dim3 grid((unsigned)((a.w + kBlockW - 1) / kBlockW), (unsigned)((a.h + kBlockH - 1) / kBlockH));
-    const int block = kBlockW * kBlockH;
+    const dim3 grid = pixel_grid(a.w, a.h);
+    const int block = kPixBlockW * kPixBlockH;
     if (bilinear && albedo)
         upsample_kernel<true, true><<<grid, block, 0, s>>>(a);
     else if (bilinear)
@@ -239,9 +233,8 @@ using namespace lrt;
 extern "C" {
 
 int lrt_upsample_default(int width, int height, int low_width, int low_height, lrt_upsample_desc* out) {
-    if (!out) return fail(LRT_E_INVALID, "out is NULL");
-    if (width < 1 || height < 1 || low_width < 1 || low_height < 1) return fail(LRT_E_INVALID, "invalid image size");
-    memset(out, 0, sizeof(*out));
+    if (int rc = frame_default_begin(out, sizeof(*out), std::min(width, low_width), std::min(height, low_height)))
+        return rc;
     out->width = width;
     out->height = height;
     out->low_width = low_width;
@@ -270,61 +263,31 @@ int lrt_upsample_host(const lrt_upsample_desc* desc, const float* color_low, con
     if (int rc = require_initialized()) return rc;
     DeviceScope ds_(0);
     hipStream_t s = ctx().stream;
-    // Every buffer goes through a device mirror of its own, all in one allocation that lives for the
-    // call and holds only the planes that are read: the RGBA frames of the low size (colour, and
-    // normal and albedo where given and read), those of the output size (normal, albedo, out), then
-    // the two id planes and the class plane if asked for, so that every RGBA mirror stays 16 B
-    // aligned. out, whose alpha stays, is copied in first.
+    // Every plane that is given and read goes through a device mirror of its own (LRT_UP_BILINEAR reads
+    // no normal). out, whose alpha stays, is copied in first.
     const bool bilinear = (desc->flags & LRT_UP_BILINEAR) != 0;
     const size_t px = (size_t)desc->width * desc->height, lpx = (size_t)desc->low_width * desc->low_height;
     const size_t quad = 16 * px, lquad = 16 * lpx, word = 4 * px, lword = 4 * lpx;
-    const float* const hlow[3] = {color_low, bilinear ? nullptr : low->normal, low->albedo};
-    const float* const hhigh[2] = {bilinear ? nullptr : high->normal, high->albedo};
-    size_t nlow = 0, nhigh = 1;   // mirrors of either size (out is one)
-    for (const float* p : hlow) nlow += p != nullptr;
-    for (const float* p : hhigh) nhigh += p != nullptr;
-    DeviceStaging<char> m;
-    if (hipMalloc(&m.p, nlow * lquad + nhigh * quad + lword + (class_out ? 2 : 1) * word) != hipSuccess)
-        return fail(LRT_E_NOMEM, "hipMalloc(upsample staging)");
-    char* at = m.p;
-    float* dlow[3];
-    float* dhigh[2];
-    for (int i = 0; i < 3; ++i) {
-        dlow[i] = hlow[i] ? reinterpret_cast<float*>(at) : nullptr;
-        if (hlow[i]) {
-            LRT_HIP(hipMemcpyAsync(dlow[i], hlow[i], lquad, hipMemcpyHostToDevice, s));
-            at += lquad;
-        }
-    }
-    for (int i = 0; i < 2; ++i) {
-        dhigh[i] = hhigh[i] ? reinterpret_cast<float*>(at) : nullptr;
-        if (hhigh[i]) {
-            LRT_HIP(hipMemcpyAsync(dhigh[i], hhigh[i], quad, hipMemcpyHostToDevice, s));
-            at += quad;
-        }
-    }
-    float* const dout = reinterpret_cast<float*>(at);
-    char* const words = at + quad;
-    int32_t* const dlid = reinterpret_cast<int32_t*>(words);
-    int32_t* const dhid = reinterpret_cast<int32_t*>(words + lword);
-    int32_t* const dcls = class_out ? reinterpret_cast<int32_t*>(words + lword + word) : nullptr;
-    LRT_HIP(hipMemcpyAsync(dout, out, quad, hipMemcpyHostToDevice, s));
-    LRT_HIP(hipMemcpyAsync(dlid, low->id, lword, hipMemcpyHostToDevice, s));
-    LRT_HIP(hipMemcpyAsync(dhid, high->id, word, hipMemcpyHostToDevice, s));
+    HostMirrors m;
+    const int color_ = m.in(color_low, lquad), lnormal_ = m.in(bilinear ? nullptr : low->normal, lquad);
+    const int lalbedo_ = m.in(low->albedo, lquad), lid_ = m.in(low->id, lword);
+    const int hnormal_ = m.in(bilinear ? nullptr : high->normal, quad), halbedo_ = m.in(high->albedo, quad);
+    const int hid_ = m.in(high->id, word);
+    const int out_ = m.inout(out, quad), class_ = m.out(class_out, word);
+    if (int rc = m.alloc("hipMalloc(upsample staging)")) return rc;
+    if (int rc = m.upload(s)) return rc;
     lrt_gbuffer dl, dh;
     memset(&dl, 0, sizeof(dl));
     memset(&dh, 0, sizeof(dh));
-    dl.normal = dlow[1];
-    dl.albedo = dlow[2];
-    dl.id = dlid;
-    dh.normal = dhigh[0];
-    dh.albedo = dhigh[1];
-    dh.id = dhid;
-    if (int rc = upsample_device(desc, dlow[0], &dl, &dh, dout, dcls, s)) return rc;
-    LRT_HIP(hipMemcpyAsync(out, dout, quad, hipMemcpyDeviceToHost, s));
-    if (class_out) LRT_HIP(hipMemcpyAsync(class_out, dcls, word, hipMemcpyDeviceToHost, s));
-    LRT_HIP(hipStreamSynchronize(s));
-    return LRT_OK;
+    dl.normal = m.dev<float>(lnormal_);
+    dl.albedo = m.dev<float>(lalbedo_);
+    dl.id = m.dev<int32_t>(lid_);
+    dh.normal = m.dev<float>(hnormal_);
+    dh.albedo = m.dev<float>(halbedo_);
+    dh.id = m.dev<int32_t>(hid_);
+    if (int rc = upsample_device(desc, m.dev<float>(color_), &dl, &dh, m.dev<float>(out_), m.dev<int32_t>(class_), s))
+        return rc;
+    return m.download(s);
 }
 
 }  // extern "C"
