@@ -708,7 +708,8 @@ int lrt_tonemap_host(const lrt_tonemap_desc* desc, const float* color, lrt_expos
  * id and depth are pinned bit for bit to the library's closest hit (lrt_accel_eval, lrt_diag.h);
  * the guides and the motion are tolerance-checked against the NumPy restatement
  * (tests/gbuffer_ref.py). Limits: whole frames, the first device, spheres only, first hits only
- * (no lens, no jitter: an edge pixel is one surface or the other, never a mixture). */
+ * (no lens, no jitter: an edge pixel is one surface or the other, never a mixture;
+ * lrt_gbuffer_chain_* further down follows the path through mirrors and glass). */
 typedef struct lrt_gbuffer_desc {
     int32_t width, height;          /* a whole frame */
     int32_t flags, reserved;        /* 0 */
@@ -1116,6 +1117,107 @@ int lrt_temporal_rectify_device(const lrt_rectify_desc* desc, const float* d_ref
 int lrt_temporal_rectify_host(const lrt_rectify_desc* desc, const float* ref, const int32_t* id,
                               const lrt_temporal_state* state, const lrt_temporal_state* out,
                               float* color_std, int32_t* class_out);
+
+/* ---- G-buffer chain: guides and path keys through mirrors and glass ---------------- */
+
+/* lrt_gbuffer_* describes the FIRST hit. On a mirror or a glass ball that is the ball, not what is
+ * seen in it: the filters find no edge inside a reflection, and the temporal stages keep a history
+ * whose reflected content changed. This pass follows the deterministic (delta) part of the path from
+ * the pixel-centre primary hit to the first surface that scatters diffusely and describes THAT
+ * surface, and it names the whole path with a key. Every consumer treats `id` as an opaque equality
+ * key (no id is ever used as an index), so `key` goes to lrt_temporal_accumulate_gbuffer_*,
+ * lrt_temporal_upsample_*, lrt_temporal_rectify_* and lrt_upsample_* in place of id, and normal,
+ * world_pos and albedo go to lrt_svgf_* and lrt_denoise_* as guides; none of those stages changes.
+ * There is no motion plane: motion, and the first-hit normal the temporal step compares, come from
+ * lrt_gbuffer_*. f32 throughout, no contraction, whole frames, row 0 at the bottom, the first
+ * device, against the scene the library holds.
+ *
+ * Per pixel:
+ *  1. Segment 0 is steps 1 and 2 of lrt_gbuffer_*, word for word (one shared header): the ray
+ *     Ray(O, D) through the pixel centre and its closest hit over (kMinT, kMaxT): (id_0, t_0),
+ *     P_0 = O + dir t_0, n_0 = normalize(P_0 - c).
+ *  2. The walk. After k followed surfaces the hit is (id_k, P_k, n_k), reached along the unit
+ *     direction d_k. The hit is DELTA iff its material is LRT_METAL with roughness <= roughness_max,
+ *     or LRT_DIELECTRIC (the type is tested first). The walk ends on a miss, on a hit that is not
+ *     delta, or once k = max_bounces; in the last case a delta hit leaves the pixel UNRESOLVED.
+ *       Metal:      d' = reflect(d_k, n_k) = d_k + 2 (-(d_k.n_k) n_k); throughput T *= albedo.
+ *       Dielectric: Scatter's geometry (parallel.cpp:149-190) without its random choice:
+ *                   dn = d_k.n_k; dn > 0: outwardN = -n_k, nint = ri; else outwardN = n_k,
+ *                   nint = 1 / ri (one IEEE division). d' = the refracted direction
+ *                   nint (d_k - outwardN dt) - outwardN sqrt(discr), dt = d_k.outwardN,
+ *                   discr = 1 - nint nint (1 - dt dt), if discr > 0; otherwise reflect(d_k, n_k)
+ *                   (total internal reflection). T is unchanged (the attenuation is 1).
+ *     The next ray is Ray(P_k, d') (one normalize), its closest hit over the same (kMinT, kMaxT)
+ *     gives (id_{k+1}, t_{k+1}), and the path length grows by t_{k+1}.
+ *  3. The key. -1 on a primary miss; id_0 where no surface was followed. Otherwise, in uint32
+ *     arithmetic (exact, wrapping): h = (uint32)id_0; for each further hit or miss j >= 1 (a miss
+ *     has id_j = -1): h = h * 0x9E3779B1 + (uint32)(id_j + 1), then h ^= h >> 15;
+ *     key = 0x40000000 | (h & 0x3FFFFFFF). A chain key is therefore never a plain id or -1. Two
+ *     different paths may share a key (30 bits); a consumer then keeps a history it could have
+ *     dropped, which is what it did on every such pixel before.
+ *  4. Outputs, each optional, at least one given:
+ *       normal, world_pos: guide_scale * (n, P) of the terminal hit, alpha written 0; 0 where the
+ *                  walk ended on the sky, as lrt_gbuffer_* writes a miss.
+ *       albedo:    guide_scale * (T * the terminal material's albedo); where the walk ended on the
+ *                  sky after at least one followed surface, guide_scale * T (the tint alone); 0 on a
+ *                  primary miss, as lrt_gbuffer_*. Alpha written 0.
+ *       key:       step 3.
+ *       id:        the terminal sphere, -1: the sky.
+ *       bounces:   the surfaces followed, plus LRT_CHAIN_UNRESOLVED on an unresolved pixel.
+ *       depth:     t_0 + t_1 + ... summed in that order; +Inf where the terminal is the sky.
+ *
+ * Two identities hold bit for bit: with max_bounces = 0 every shared plane equals lrt_gbuffer_*'s on
+ * any scene (key = id = its id; bounces = 0, or LRT_CHAIN_UNRESOLVED on a delta first hit); and for
+ * any max_bounces the same holds at every pixel whose first hit is not delta.
+ *
+ * key, id and bounces are compared exactly, the float planes by tolerance, against the NumPy
+ * restatement (tests/gbuffer_chain_ref.py). Limits: the chain is the deterministic branch only
+ * (glass shows its refraction, never its Fresnel reflection; a rough metal below roughness_max is
+ * followed as if polished). No reflection motion vector: under a moving camera the key test rejects
+ * the history of a reflection where a motion vector would reproject it. A terminal on the sky has
+ * zero normal and position. Spheres only, whole frames, the first device. */
+#define LRT_CHAIN_MAX_BOUNCES 16
+#define LRT_CHAIN_UNRESOLVED 0x100
+typedef struct lrt_gbuffer_chain_desc {
+    int32_t width, height;          /* a whole frame */
+    int32_t flags, reserved;        /* 0 */
+    lrt_camera camera;
+    int32_t max_bounces;            /* 0..LRT_CHAIN_MAX_BOUNCES; default 4 */
+    float roughness_max;            /* finite, >= 0; default 0.25 */
+    float guide_scale;              /* finite, > 0; default 1 (lrt_gbuffer_desc.guide_scale's role) */
+    int32_t reserved2;              /* 0 */
+} lrt_gbuffer_chain_desc;
+
+typedef struct lrt_gbuffer_chain {  /* every member optional, at least one non-NULL */
+    float* normal;      /* RGBA quads: rgb = guide_scale * terminal n, alpha written 0 */
+    float* world_pos;   /* RGBA quads: rgb = guide_scale * terminal P, alpha written 0 */
+    float* albedo;      /* RGBA quads: rgb = guide_scale * T * terminal albedo, alpha written 0 */
+    int32_t* key;       /* width*height: the path key */
+    int32_t* id;        /* width*height: the terminal sphere, -1: the sky */
+    int32_t* bounces;   /* width*height: surfaces followed (+ LRT_CHAIN_UNRESOLVED) */
+    float* depth;       /* width*height: the path's length; +Inf where it ends on the sky */
+} lrt_gbuffer_chain;
+
+/* The defaults for a width x height frame and a camera: max_bounces 4, roughness_max 0.25,
+ * guide_scale 1. Choices, not tuned values: on the default scene 0.25 follows spheres 3, 4 and 5
+ * and stops at sphere 6 (roughness 0.6). */
+int lrt_gbuffer_chain_default(int width, int height, const lrt_camera* camera, lrt_gbuffer_chain_desc* out);
+
+/* The pass into device buffers. Only the planes given are written. Scenes of up to 16 spheres are
+ * scanned, larger ones go through the uniform grid (built on first use, as a render would).
+ *
+ * LRT_E_INVALID, before any device use: NULL desc or d_out, or all seven planes NULL; sizes < 1 or
+ * width * height > INT_MAX / 4; flags, reserved or reserved2 != 0; max_bounces outside
+ * 0..LRT_CHAIN_MAX_BOUNCES; roughness_max not finite or < 0; guide_scale not finite or <= 0; any two
+ * planes overlapping by address range (16 bytes per pixel for the quads, 4 for key, id, bounces and
+ * depth). Then LRT_E_STATE without lrt_initialize(). Asynchronous on `stream` and ordered only
+ * against it, with no host round trip and no scratch; it sees the scene as an lrt_render_device
+ * call made at the same moment would. Acts on the first device. */
+int lrt_gbuffer_chain_device(const lrt_gbuffer_chain_desc* desc, const lrt_gbuffer_chain* d_out, void* stream);
+
+/* Same into HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_gbuffer_chain_device's bit for bit. */
+int lrt_gbuffer_chain_host(const lrt_gbuffer_chain_desc* desc, const lrt_gbuffer_chain* out);
 
 #ifdef __cplusplus
 }

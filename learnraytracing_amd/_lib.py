@@ -175,6 +175,28 @@ GBUFFER_GUIDE_NAMES = ("normal", "world_pos", "albedo")   # always returned
 GBUFFER_EXTRA_NAMES = ("id", "depth", "motion")           # on request
 GBUFFER_NAMES = GBUFFER_GUIDE_NAMES + GBUFFER_EXTRA_NAMES
 
+CHAIN_MAX_BOUNCES = 16      # LRT_CHAIN_MAX_BOUNCES
+CHAIN_UNRESOLVED = 0x100    # LRT_CHAIN_UNRESOLVED, in the bounces plane
+
+
+class GbufferChainDesc(ctypes.Structure):    # lrt_gbuffer_chain_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("camera", Camera),
+                ("max_bounces", ctypes.c_int32), ("roughness_max", ctypes.c_float),
+                ("guide_scale", ctypes.c_float), ("reserved2", ctypes.c_int32)]
+
+
+class GbufferChain(ctypes.Structure):         # lrt_gbuffer_chain
+    _fields_ = [("normal", ctypes.c_void_p), ("world_pos", ctypes.c_void_p), ("albedo", ctypes.c_void_p),
+                ("key", ctypes.c_void_p), ("id", ctypes.c_void_p), ("bounces", ctypes.c_void_p),
+                ("depth", ctypes.c_void_p)]
+
+
+GBUFFER_CHAIN_GUIDE_NAMES = ("normal", "world_pos", "albedo")   # RGBA quads
+GBUFFER_CHAIN_INT_NAMES = ("key", "id", "bounces")              # int32 [height, width]
+GBUFFER_CHAIN_NAMES = GBUFFER_CHAIN_GUIDE_NAMES + GBUFFER_CHAIN_INT_NAMES + ("depth",)
+
 
 class TemporalGbufferDesc(ctypes.Structure):  # lrt_temporal_gbuffer_desc
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -322,6 +344,9 @@ SIGNATURES = {
                                          _c.POINTER(TemporalState), _vp, _vp, _vp]),
     "lrt_temporal_rectify_host": (_i, [_c.POINTER(RectifyDesc), _vp, _vp, _c.POINTER(TemporalState),
                                        _c.POINTER(TemporalState), _vp, _vp]),
+    "lrt_gbuffer_chain_default": (_i, [_i, _i, _c.POINTER(Camera), _c.POINTER(GbufferChainDesc)]),
+    "lrt_gbuffer_chain_device": (_i, [_c.POINTER(GbufferChainDesc), _c.POINTER(GbufferChain), _vp]),
+    "lrt_gbuffer_chain_host": (_i, [_c.POINTER(GbufferChainDesc), _c.POINTER(GbufferChain)]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

@@ -9,6 +9,7 @@
 // render units: id and depth are pinned bit for bit to lrt_accel_eval.
 #include "lrt_internal.h"
 #include "lrt_pixel.h"
+#include "lrt_primary.h"
 
 namespace lrt {
 
@@ -48,11 +49,12 @@ __device__ __forceinline__ void gbuffer_pixel(const GbufferArgs& a, const float4
     const int x = block_x(), y = block_y();
     if (x >= a.w || y >= a.h) return;
     const size_t ip = (size_t)y * a.w + x;
-    const float s = ((float)x + 0.5f) * a.rw, t = ((float)y + 0.5f) * a.rh;
-    const F3 D = ((a.L + s * a.H) + t * a.V) - a.O;
-    const Ray r = make_ray(a.O, D);
-    float tHit;
-    const int id = kGrid ? ClosestHitGrid(r.orig, r.dir, a.gv, tHit) : ClosestHit(r.orig, r.dir, a.sph, a.count, tHit);
+    // steps 1 and 2, shared with lrt_gbuffer_chain.hip (its segment 0)
+    const PrimaryHit ph = primary_hit<kGrid>(x, y, a.rw, a.rh, a.O, a.L, a.H, a.V, a.sph, a.count, a.gv);
+    const F3 D = ph.D;
+    const Ray r = ph.r;
+    const float tHit = ph.t;
+    const int id = ph.id;
     const bool hit = id >= 0;
     F3 P = f3(0.0f, 0.0f, 0.0f), n = P, alb = P, c = P;
     if (hit) {

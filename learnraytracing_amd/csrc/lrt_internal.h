@@ -18,6 +18,7 @@
 //   lrt_svgf.hip      the variance-guided filter over the temporal state (lrt_svgf_*): kernels and entry points
 //   lrt_tonemap.hip   auto-exposure metering and tone mapping (lrt_tonemap_*): kernels and entry points
 //   lrt_gbuffer.hip   the pixel-centre G-buffer pass (lrt_gbuffer_*): kernel and entry points
+//   lrt_gbuffer_chain.hip  the G-buffer followed through mirrors and glass (lrt_gbuffer_chain_*): kernel and entry points
 //   lrt_upsample.hip  G-buffer-guided upsampling of a low-resolution frame (lrt_upsample_*): kernel and entry points
 //   lrt_temporal_upsample.hip  a full-resolution history from jittered low frames (lrt_temporal_upsample_*, lrt_camera_jitter)
 //   lrt_rectify.hip   history rectification (lrt_temporal_rectify_*): the LDS-tiled window kernel and entry points

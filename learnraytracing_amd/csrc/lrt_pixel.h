@@ -1,6 +1,6 @@
 // The pixel map, the launch grid and the colour store that the one-thread-per-pixel post-process
 // kernels share (lrt_temporal, lrt_temporal_gbuffer, lrt_temporal_upsample, lrt_upsample,
-// lrt_gbuffer; lrt_rectify takes the store only). Nothing here multiplies and adds, so the header
+// lrt_gbuffer, lrt_gbuffer_chain; lrt_rectify takes the store only). Nothing here multiplies and adds, so the header
 // needs no contraction pragma. Every kernel that uses it compiles to the instructions it had with
 // these lines in its own text (tools/isa_same.sh).
 #pragma once

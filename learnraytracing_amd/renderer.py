@@ -1252,6 +1252,110 @@ def gbuffer_tensor(width: int, height: int, camera: L.Camera, prev_camera: Optio
                          spheres, prev_spheres, (ctypes.c_void_p(s.cuda_stream),))
 
 
+# ---- G-buffer chain: guides and path keys through mirrors and glass -------------------------
+def gbuffer_chain_desc(width: int, height: int, camera: L.Camera, max_bounces: int = 4, roughness_max: float = 0.25,
+                       guide_scale: float = 1.0) -> L.GbufferChainDesc:
+    """lrt_gbuffer_chain_default for a width x height frame seen from `camera`, with max_bounces
+    (0..CHAIN_MAX_BOUNCES), roughness_max and guide_scale set."""
+    if not isinstance(camera, L.Camera):
+        raise L.LrtError(L.LRT_E_INVALID, "camera must be a Camera struct")
+    d = L.GbufferChainDesc()
+    L.check(L.lib().lrt_gbuffer_chain_default(int(width), int(height), ctypes.byref(camera), ctypes.byref(d)))
+    d.max_bounces = int(max_bounces)
+    d.roughness_max = float(roughness_max)
+    d.guide_scale = float(guide_scale)
+    return d
+
+
+def _gbuffer_chain_call(entry, out, which, make, ptr, check, extra):
+    """The marshalling the host and tensor front ends share. out: the caller's planes {name: buffer}
+    (only those are written), or None for new ones: all seven but those `which` sets False."""
+    for name in which:
+        if name not in L.GBUFFER_CHAIN_NAMES:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown chain plane {name!r}")
+    if out is None:
+        out = {name: make(name) for name in L.GBUFFER_CHAIN_NAMES if which.get(name, True)}
+    g = L.GbufferChain()
+    for name, buf in out.items():
+        if name not in L.GBUFFER_CHAIN_NAMES:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown chain plane {name!r}")
+        check(buf, name)
+        setattr(g, name, ptr(buf))
+    L.check(entry(ctypes.byref(g), *extra))
+    return out
+
+
+def gbuffer_chain_host(width: int, height: int, camera: L.Camera, max_bounces: int = 4, roughness_max: float = 0.25,
+                       guide_scale: float = 1.0, out: Optional[dict] = None, **which) -> dict:
+    """The G-buffer of the current scene followed through mirrors and glass (lrt_gbuffer_chain_host):
+    from the pixel-centre first hit along reflect / refract through every Metal of roughness <=
+    roughness_max and every Dielectric, up to max_bounces surfaces, to the first surface that
+    scatters diffusely. Returns {"normal", "world_pos", "albedo"} as float32 [height, width, 4]
+    (that surface's, each times guide_scale, the albedo tinted by the mirrors on the way), "key"
+    (int32 [height, width]: the path key, the first hit's id where nothing was followed), "id" (the
+    terminal sphere, -1: the sky), "bounces" (the surfaces followed, plus CHAIN_UNRESOLVED where the
+    walk stopped on a delta surface) and "depth" (float32 [height, width]: the path's length, +Inf
+    on the sky). which: name=False leaves a plane out. out: the caller's planes instead, any subset
+    of the seven names; only those are written.
+
+    The composition with the stages that exist (none of them changes; motion and the first-hit
+    normal come from gbuffer_*):
+      TemporalAccumulator.step_gbuffer(color, {"normal": g["normal"], "motion": g["motion"],
+                                               "id": chain["key"]})   # ping-pong two key tensors, as the planes
+      temporal_rectify_tensor(..., id=chain["key"])
+      svgf_filter_tensor / denoise_tensor with chain["normal"], chain["world_pos"], chain["albedo"] as guides
+      upsample_tensor with "key" as "id" in both G-buffers."""
+    w, h = int(width), int(height)
+    d = gbuffer_chain_desc(w, h, camera, max_bounces, roughness_max, guide_scale)
+
+    def kind(name):
+        return (1, np.int32) if name in L.GBUFFER_CHAIN_INT_NAMES else (1 if name == "depth" else 4, np.float32)
+
+    def make(name):
+        k, dt = kind(name)
+        return np.zeros((h, w) if k == 1 else (h, w, 4), dt)
+
+    def check(buf, name):
+        k, dt = kind(name)
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < w * h * k:
+            raise L.LrtError(L.LRT_E_INVALID,
+                             f"{name} must be a C-contiguous {np.dtype(dt).name} array of >= {w * h * k} elements")
+
+    return _gbuffer_chain_call(lambda *a: L.lib().lrt_gbuffer_chain_host(ctypes.byref(d), *a), out, which, make,
+                               lambda b: b.ctypes.data, check, ())
+
+
+def gbuffer_chain_tensor(width: int, height: int, camera: L.Camera, max_bounces: int = 4, roughness_max: float = 0.25,
+                         guide_scale: float = 1.0, out: Optional[dict] = None, stream=None, device="cuda:0",
+                         **which) -> dict:
+    """gbuffer_chain_host into cuda tensors (lrt_gbuffer_chain_device): asynchronous on `stream` (a
+    torch.cuda.Stream, default: current) and ordered only against it. "key", "id" and "bounces" are
+    int32 tensors, the others float32. The composition is gbuffer_chain_host's."""
+    import torch
+
+    w, h = int(width), int(height)
+    d = gbuffer_chain_desc(w, h, camera, max_bounces, roughness_max, guide_scale)
+    dev = next(iter(out.values())).device if out else torch.device(device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+
+    def kind(name):
+        return (1, torch.int32) if name in L.GBUFFER_CHAIN_INT_NAMES else (1 if name == "depth" else 4, torch.float32)
+
+    def make(name):
+        k, dt = kind(name)
+        with torch.cuda.stream(s):
+            return torch.zeros((h, w) if k == 1 else (h, w, 4), dtype=dt, device=dev)
+
+    def check(t, name):
+        k, dt = kind(name)
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()
+                and t.numel() >= w * h * k):
+            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a contiguous cuda {dt} tensor of >= {w * h * k} elements")
+
+    return _gbuffer_chain_call(lambda *a: L.lib().lrt_gbuffer_chain_device(ctypes.byref(d), *a), out, which, make,
+                               lambda t: t.data_ptr(), check, (ctypes.c_void_p(s.cuda_stream),))
+
+
 # ---- G-buffer-guided upsampling of a low-resolution frame -----------------------------------
 def upsample_desc(width: int, height: int, low_width: int, low_height: int, **params) -> L.UpsampleDesc:
     """lrt_upsample_default for a width x height frame from a low_width x low_height one, with any of
