@@ -1173,9 +1173,10 @@ int lrt_temporal_rectify_host(const lrt_rectify_desc* desc, const float* ref, co
  * key, id and bounces are compared exactly, the float planes by tolerance, against the NumPy
  * restatement (tests/gbuffer_chain_ref.py). Limits: the chain is the deterministic branch only
  * (glass shows its refraction, never its Fresnel reflection; a rough metal below roughness_max is
- * followed as if polished). No reflection motion vector: under a moving camera the key test rejects
- * the history of a reflection where a motion vector would reproject it. A terminal on the sky has
- * zero normal and position. Spheres only, whole frames, the first device. */
+ * followed as if polished). This pass writes no motion plane: the motion vector of what a followed
+ * pixel shows is lrt_gbuffer_chain_motion_*'s, further down; with lrt_gbuffer_*'s first-hit motion
+ * alone a reflection is reprojected as the ball's surface. A terminal on the sky has zero normal and
+ * position. Spheres only, whole frames, the first device. */
 #define LRT_CHAIN_MAX_BOUNCES 16
 #define LRT_CHAIN_UNRESOLVED 0x100
 typedef struct lrt_gbuffer_chain_desc {
@@ -1218,6 +1219,118 @@ int lrt_gbuffer_chain_device(const lrt_gbuffer_chain_desc* desc, const lrt_gbuff
 /* Same into HOST buffers: staged through device memory, blocking; every output equals
  * lrt_gbuffer_chain_device's bit for bit. */
 int lrt_gbuffer_chain_host(const lrt_gbuffer_chain_desc* desc, const lrt_gbuffer_chain* out);
+
+/* ---- G-buffer chain motion: motion vectors inside mirrors and glass --------------- */
+
+/* lrt_gbuffer_*'s motion is the motion of the FIRST hit: on a mirror or a glass ball, of the ball's
+ * surface, not of what is seen in it. For every pixel whose chain (lrt_gbuffer_chain_*) followed at
+ * least one surface this pass finds the position q in the PREVIOUS frame whose chain, under the
+ * previous camera and scene, ends at the same surface point, and writes motion = q - p in
+ * lrt_gbuffer_*'s layout. Everywhere else, and wherever the search fails, it copies the first-hit
+ * motion it was given, bit for bit. The plane goes where `motion` goes
+ * (lrt_temporal_accumulate_gbuffer_*, lrt_temporal_upsample_*, lrt_temporal_rectify_*), with the
+ * chain's key as id; no stage changes. Every surface is a sphere and glass refracts, so there is no
+ * closed form: the definition is a search with a fixed number of steps, and it checks its own
+ * answer. f32 throughout, no contraction, whole frames, row 0 at the bottom, the first device.
+ *
+ * chain(C, S, fx, fy) is the chain at a continuous pixel position under camera C and spheres S:
+ * s = (fx + 0.5f) * (1.0f / (float)width), t = (fy + 0.5f) * (1.0f / (float)height) (the host's
+ * reciprocals), D = ((L + s H) + t V) - O, the ray Ray(O, D), its closest hit, then the walk of
+ * lrt_gbuffer_chain_* step 2 and the key of step 3, unchanged (materials: the current ones). At
+ * integer fx, fy it is lrt_gbuffer_chain_*'s pixel. It yields the key, the terminal id, the bounces
+ * and the terminal vector F: the terminal point P on a hit, the last ray's unit direction where the
+ * walk ends on the sky.
+ *
+ * Per pixel (x, y):
+ *  1. (K, j, b, Y) = chain(camera, the current spheres, x, y). Nothing followed (a primary miss
+ *     included): LRT_CM_NOT_FOLLOWED. Unresolved after at least one surface: LRT_CM_UNRESOLVED.
+ *  2. The target Y'. If j >= 0, `scene` is given and sphere j's eight floats differ in a bit between
+ *     scene->spheres and scene->prev_spheres: Y' = c' + (r' / r) (Y - c), lrt_gbuffer_*'s carry-back.
+ *     Otherwise Y' = Y. With `scene` given, r' <= 0 or r <= 0 of sphere j: LRT_CM_NO_SEED.
+ *  3. The seed q = (x + mx, y + my) of first_motion's quad (mx, my, ., mw). mw == 0, or a q that
+ *     fails |q.x|, |q.y| < 1e6 (a NaN fails): LRT_CM_NO_SEED. This is the test of step 1 of
+ *     lrt_temporal_accumulate_gbuffer_*: a vector that stage would not take is not searched from.
+ *  4. `iterations` times: F0 = chain(prev_camera, the previous spheres, q), Fx at q + (probe_px, 0),
+ *     Fy at q + (0, probe_px). Any of the three keys other than K: LRT_CM_KEY_LOST.
+ *     Jx = (Fx - F0) (1 / probe_px), Jy = (Fy - F0) (1 / probe_px) (one host division), r = Y' - F0;
+ *     a = Jx.Jx, bb = Jx.Jy, c = Jy.Jy, e = Jx.r, f = Jy.r, det = a c - bb bb;
+ *     dx = (c e - bb f) / det, dy = (a f - bb e) / det. A dx or dy that is not finite:
+ *     LRT_CM_NOT_CONVERGED. len = sqrt(dx dx + dy dy); if len > step_max_px both are multiplied by
+ *     step_max_px / len. q += (dx, dy); a q that fails |q.x|, |q.y| < 1e6: LRT_CM_NOT_CONVERGED
+ *     (no ray is cast from there; the defaults move q by at most 48 pixels).
+ *  5. F0 = chain(prev_camera, the previous spheres, q); a key other than K: LRT_CM_KEY_LOST.
+ *     (dx, dy) as above with the LAST iteration's Jx and Jy and the new r; rem = sqrt(dx dx + dy dy).
+ *     LRT_CM_CONVERGED iff rem <= converged_px and |q.x|, |q.y| < 1e6 (a NaN fails); otherwise
+ *     LRT_CM_NOT_CONVERGED.
+ *  6. Outputs, each optional, at least one given:
+ *       motion: where LRT_CM_CONVERGED, (q.x - x, q.y - y, first_motion's third word, 1); everywhere
+ *               else first_motion's quad, its four words unchanged.
+ *       status: the LRT_CM_* constant.
+ * The iteration count is fixed and there is no early exit. A static frame has r = 0 and a step of
+ * exactly 0: under bit-identical cameras and an unmoved scene, motion equals first_motion at every
+ * pixel, bit for bit. A pixel costs 1 + 3 iterations + 1 walks: 11 at the defaults.
+ *
+ * `scene` follows lrt_gbuffer_device's rules and must have at most 16 spheres (the scanned scenes:
+ * the previous spheres travel in the kernel's arguments). With `scene` NULL the previous scene is
+ * the current one, at any count; above 16 spheres the walks go through the uniform grid.
+ *
+ * status is compared exactly and motion by tolerance against the NumPy restatement
+ * (tests/gbuffer_chain_motion_ref.py). Limits: the search needs the previous frame to have shown
+ * the same path key: content newly reflected falls back to the first-hit motion, and the key test
+ * of the temporal stages then drops it, as before. A silhouette pixel whose probe crosses a key
+ * boundary falls back too. Glass shows its refraction only (the chain's limit). Scene motion up to
+ * 16 spheres; the previous materials are the current ones. Spheres only, whole frames, the first
+ * device. */
+#define LRT_CM_NOT_FOLLOWED 0   /* the chain followed nothing: first_motion is the pixel's motion */
+#define LRT_CM_CONVERGED 1      /* motion was written */
+#define LRT_CM_UNRESOLVED 2     /* the chain is LRT_CHAIN_UNRESOLVED */
+#define LRT_CM_NO_SEED 3        /* first_motion is not projectable, or the terminal sphere did not exist */
+#define LRT_CM_KEY_LOST 4       /* an evaluation in the previous frame had another path key */
+#define LRT_CM_NOT_CONVERGED 5  /* a step was not finite, or the remaining step exceeds converged_px */
+#define LRT_CM_MAX_ITERATIONS 8
+typedef struct lrt_gbuffer_chain_motion_desc {
+    int32_t width, height;          /* a whole frame */
+    int32_t flags, reserved;        /* 0 */
+    lrt_camera camera, prev_camera;
+    int32_t max_bounces;            /* 0..LRT_CHAIN_MAX_BOUNCES; default 4 (the chain desc's) */
+    float roughness_max;            /* finite, >= 0; default 0.25 (the chain desc's) */
+    int32_t iterations;             /* 1..LRT_CM_MAX_ITERATIONS; default 3 */
+    float probe_px;                 /* finite, > 0; default 0.25 */
+    float step_max_px;              /* finite, > 0; default 16 */
+    float converged_px;             /* finite, > 0; default 0.0625 */
+    int32_t reserved2, reserved3;   /* 0 */
+} lrt_gbuffer_chain_motion_desc;
+
+typedef struct lrt_gbuffer_chain_motion {  /* both optional, at least one non-NULL */
+    float* motion;      /* RGBA quads, all four written (lrt_gbuffer.motion's layout) */
+    int32_t* status;    /* width*height: LRT_CM_* */
+} lrt_gbuffer_chain_motion;
+
+/* The defaults for a width x height frame and a camera pair: the chain's max_bounces 4 and
+ * roughness_max 0.25, iterations 3, probe_px 0.25, step_max_px 16, converged_px 0.0625.
+ * prev_camera == NULL: the camera. */
+int lrt_gbuffer_chain_motion_default(int width, int height, const lrt_camera* camera, const lrt_camera* prev_camera,
+                                     lrt_gbuffer_chain_motion_desc* out);
+
+/* The pass into device buffers. d_first_motion: the motion plane of an lrt_gbuffer_* call for the
+ * same camera pair and scene pair (width*height RGBA quads), required. `scene` may be NULL; if given
+ * it is read from host memory before the call returns. Only the planes given are written.
+ *
+ * LRT_E_INVALID, before any device use: NULL desc or d_out, or both planes NULL; sizes < 1 or
+ * width * height > INT_MAX / 4; flags or a reserved word != 0; max_bounces outside
+ * 0..LRT_CHAIN_MAX_BOUNCES; roughness_max not finite or < 0; iterations outside
+ * 1..LRT_CM_MAX_ITERATIONS; probe_px, step_max_px or converged_px not finite or <= 0; a prev_camera
+ * that lrt_temporal_* rejects; d_first_motion NULL; an output overlapping d_first_motion or the other
+ * output by address range; with `scene`, what lrt_gbuffer_device refuses, or a count above 16. Then
+ * LRT_E_STATE without lrt_initialize(). Asynchronous on `stream` and ordered only against it, with
+ * no host round trip and no scratch. Acts on the first device. */
+int lrt_gbuffer_chain_motion_device(const lrt_gbuffer_chain_motion_desc* desc, const lrt_scene_motion* scene,
+                                    const float* d_first_motion, const lrt_gbuffer_chain_motion* d_out, void* stream);
+
+/* Same with HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_gbuffer_chain_motion_device's bit for bit. */
+int lrt_gbuffer_chain_motion_host(const lrt_gbuffer_chain_motion_desc* desc, const lrt_scene_motion* scene,
+                                  const float* first_motion, const lrt_gbuffer_chain_motion* out);
 
 #ifdef __cplusplus
 }

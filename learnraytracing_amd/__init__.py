@@ -18,6 +18,7 @@ from .renderer import (DrawTest, InitializeDevices, InitializeTest, Job, Shutdow
                        tonemap_desc, tonemap_host, tonemap_tensor,
                        gbuffer_desc, gbuffer_host, gbuffer_tensor,
                        gbuffer_chain_desc, gbuffer_chain_host, gbuffer_chain_tensor,
+                       gbuffer_chain_motion_desc, gbuffer_chain_motion_host, gbuffer_chain_motion_tensor,
                        upsample_desc, upsample_host, upsample_tensor,
                        TemporalUpsampler, jitter_camera, jitter_phases, temporal_upsample_desc,
                        temporal_upsample_host, temporal_upsample_tensor,

@@ -197,6 +197,28 @@ GBUFFER_CHAIN_GUIDE_NAMES = ("normal", "world_pos", "albedo")   # RGBA quads
 GBUFFER_CHAIN_INT_NAMES = ("key", "id", "bounces")              # int32 [height, width]
 GBUFFER_CHAIN_NAMES = GBUFFER_CHAIN_GUIDE_NAMES + GBUFFER_CHAIN_INT_NAMES + ("depth",)
 
+# LRT_CM_*: the status plane of lrt_gbuffer_chain_motion_*
+CM_NOT_FOLLOWED, CM_CONVERGED, CM_UNRESOLVED, CM_NO_SEED, CM_KEY_LOST, CM_NOT_CONVERGED = range(6)
+CM_MAX_ITERATIONS = 8       # LRT_CM_MAX_ITERATIONS
+
+
+class GbufferChainMotionDesc(ctypes.Structure):   # lrt_gbuffer_chain_motion_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("camera", Camera), ("prev_camera", Camera),
+                ("max_bounces", ctypes.c_int32), ("roughness_max", ctypes.c_float),
+                ("iterations", ctypes.c_int32), ("probe_px", ctypes.c_float),
+                ("step_max_px", ctypes.c_float), ("converged_px", ctypes.c_float),
+                ("reserved2", ctypes.c_int32), ("reserved3", ctypes.c_int32)]
+
+
+class GbufferChainMotion(ctypes.Structure):       # lrt_gbuffer_chain_motion
+    _fields_ = [("motion", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+GBUFFER_CHAIN_MOTION_NAMES = ("motion", "status")
+GBUFFER_CHAIN_MOTION_PARAMS = ("max_bounces", "roughness_max", "iterations", "probe_px", "step_max_px", "converged_px")
+
 
 class TemporalGbufferDesc(ctypes.Structure):  # lrt_temporal_gbuffer_desc
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -347,6 +369,12 @@ SIGNATURES = {
     "lrt_gbuffer_chain_default": (_i, [_i, _i, _c.POINTER(Camera), _c.POINTER(GbufferChainDesc)]),
     "lrt_gbuffer_chain_device": (_i, [_c.POINTER(GbufferChainDesc), _c.POINTER(GbufferChain), _vp]),
     "lrt_gbuffer_chain_host": (_i, [_c.POINTER(GbufferChainDesc), _c.POINTER(GbufferChain)]),
+    "lrt_gbuffer_chain_motion_default": (_i, [_i, _i, _c.POINTER(Camera), _c.POINTER(Camera),
+                                              _c.POINTER(GbufferChainMotionDesc)]),
+    "lrt_gbuffer_chain_motion_device": (_i, [_c.POINTER(GbufferChainMotionDesc), _c.POINTER(SceneMotion), _vp,
+                                             _c.POINTER(GbufferChainMotion), _vp]),
+    "lrt_gbuffer_chain_motion_host": (_i, [_c.POINTER(GbufferChainMotionDesc), _c.POINTER(SceneMotion), _vp,
+                                           _c.POINTER(GbufferChainMotion)]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

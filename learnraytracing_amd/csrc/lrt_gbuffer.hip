@@ -157,18 +157,6 @@ static int validate_gbuffer(const lrt_gbuffer_desc* d, const lrt_scene_motion* s
     return LRT_OK;
 }
 
-// `scene` against the scene the library holds (the caller holds g_mu; host memory only). Without
-// lrt_initialize() there is no scene to agree with.
-static int validate_current_scene(const lrt_scene_motion* sm) {
-    if (!sm) return LRT_OK;
-    const Context& c = g_devs[0];
-    const int have = c.ready ? (int)c.spheres.size() : 0;
-    if (sm->count != have) return fail(LRT_E_INVALID, "scene: count differs from the current scene's");
-    if (memcmp(sm->spheres, c.spheres.data(), sizeof(lrt_sphere) * (size_t)have) != 0)
-        return fail(LRT_E_INVALID, "scene: spheres are not the current scene's");
-    return LRT_OK;
-}
-
 // The pass on stream s (device pointers, validated; context 0 is current).
 static int gbuffer_device(const lrt_gbuffer_desc* d, const lrt_scene_motion* sm, const lrt_gbuffer* o, hipStream_t s) {
     Context& c = ctx();

@@ -19,6 +19,7 @@
 //   lrt_tonemap.hip   auto-exposure metering and tone mapping (lrt_tonemap_*): kernels and entry points
 //   lrt_gbuffer.hip   the pixel-centre G-buffer pass (lrt_gbuffer_*): kernel and entry points
 //   lrt_gbuffer_chain.hip  the G-buffer followed through mirrors and glass (lrt_gbuffer_chain_*): kernel and entry points
+//   lrt_gbuffer_chain_motion.hip  motion vectors inside mirrors and glass (lrt_gbuffer_chain_motion_*): kernel and entry points
 //   lrt_upsample.hip  G-buffer-guided upsampling of a low-resolution frame (lrt_upsample_*): kernel and entry points
 //   lrt_temporal_upsample.hip  a full-resolution history from jittered low frames (lrt_temporal_upsample_*, lrt_camera_jitter)
 //   lrt_rectify.hip   history rectification (lrt_temporal_rectify_*): the LDS-tiled window kernel and entry points
@@ -594,6 +595,17 @@ inline int validate_scene_motion(const lrt_scene_motion* sm) {
         for (int i = 0; i < sm->count; ++i)
             for (float v : {arr[i].center.x, arr[i].center.y, arr[i].center.z, arr[i].radius})
                 if (!std::isfinite(v)) return fail(LRT_E_INVALID, "spheres must be finite");
+    return LRT_OK;
+}
+// An lrt_scene_motion's `spheres` against the scene the library holds (the caller holds g_mu; host
+// memory only). Without lrt_initialize() there is no scene to agree with.
+inline int validate_current_scene(const lrt_scene_motion* sm) {
+    if (!sm) return LRT_OK;
+    const Context& c = g_devs[0];
+    const int have = c.ready ? (int)c.spheres.size() : 0;
+    if (sm->count != have) return fail(LRT_E_INVALID, "scene: count differs from the current scene's");
+    if (memcmp(sm->spheres, c.spheres.data(), sizeof(lrt_sphere) * (size_t)have) != 0)
+        return fail(LRT_E_INVALID, "scene: spheres are not the current scene's");
     return LRT_OK;
 }
 

@@ -1356,6 +1356,121 @@ def gbuffer_chain_tensor(width: int, height: int, camera: L.Camera, max_bounces:
                                lambda t: t.data_ptr(), check, (ctypes.c_void_p(s.cuda_stream),))
 
 
+# ---- G-buffer chain motion: motion vectors inside mirrors and glass -------------------------
+def gbuffer_chain_motion_desc(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera] = None,
+                              **params) -> L.GbufferChainMotionDesc:
+    """lrt_gbuffer_chain_motion_default for a width x height frame seen from `camera`, the previous
+    frame from `prev_camera` (None: the same camera), with any of max_bounces, roughness_max,
+    iterations, probe_px, step_max_px, converged_px overridden."""
+    if not isinstance(camera, L.Camera) or not (prev_camera is None or isinstance(prev_camera, L.Camera)):
+        raise L.LrtError(L.LRT_E_INVALID, "camera and prev_camera must be Camera structs")
+    d = L.GbufferChainMotionDesc()
+    L.check(L.lib().lrt_gbuffer_chain_motion_default(int(width), int(height), ctypes.byref(camera),
+                                                     ctypes.byref(prev_camera) if prev_camera is not None else None,
+                                                     ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.GBUFFER_CHAIN_MOTION_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown chain motion parameter {name!r}")
+        setattr(d, name, int(v) if name in ("max_bounces", "iterations") else float(v))
+    return d
+
+
+def _gbuffer_chain_motion_call(entry, first_motion, out, want, make, ptr, check, spheres, prev_spheres, extra):
+    """The marshalling the host and tensor front ends share. out: the caller's planes {name: buffer}
+    (only those are written), or None for new ones: those `want` names."""
+    if out is None:
+        out = {name: make(name) for name in L.GBUFFER_CHAIN_MOTION_NAMES if want[name]}
+    g = L.GbufferChainMotion()
+    for name, buf in out.items():
+        if name not in L.GBUFFER_CHAIN_MOTION_NAMES:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown chain motion plane {name!r}")
+        check(buf, name)
+        setattr(g, name, ptr(buf))
+    check(first_motion, "first_motion")
+    sm = None
+    if prev_spheres is not None:
+        sm = _scene_motion(spheres if spheres is not None else get_scene()[0], prev_spheres)
+    elif spheres is not None:
+        raise L.LrtError(L.LRT_E_INVALID, "spheres needs prev_spheres")
+    L.check(entry(ctypes.byref(sm) if sm is not None else None, ctypes.c_void_p(ptr(first_motion)), ctypes.byref(g), *extra))
+    return out
+
+
+def gbuffer_chain_motion_host(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera],
+                              first_motion: np.ndarray, spheres=None, prev_spheres=None, motion: bool = True,
+                              status: bool = True, out: Optional[dict] = None, **params) -> dict:
+    """Motion vectors of what mirrors and glass SHOW (lrt_gbuffer_chain_motion_host). first_motion is
+    gbuffer_*'s "motion" for the same camera pair and scene pair (float32 [height, width, 4]); for every
+    pixel whose chain followed a surface the pass searches the previous frame for the position whose
+    chain ends at the same surface point. Returns {"motion": float32 [height, width, 4], gbuffer_*'s
+    layout: the found vector where the search converged, first_motion's quad bit for bit everywhere
+    else; "status": int32 [height, width], CM_*}. prev_spheres: the previous frame's scene where
+    spheres moved (at most 16 spheres), spheres: the current one (default: what the library holds).
+    motion / status = False leaves a plane out. out: the caller's planes instead; only those are
+    written. params: max_bounces and roughness_max (the chain's), iterations, probe_px, step_max_px,
+    converged_px.
+
+    The composition (no stage changes): with g = gbuffer_*(motion=True), chain = gbuffer_chain_* and
+    cm = this pass,
+      TemporalAccumulator.step_gbuffer(color, {"normal": g["normal"], "motion": cm["motion"],
+                                               "id": chain["key"]})
+    and likewise "motion" of temporal_upsample_* and temporal_rectify_*."""
+    w, h = int(width), int(height)
+    d = gbuffer_chain_motion_desc(w, h, camera, prev_camera, **params)
+
+    def kind(name):
+        return (1, np.int32) if name == "status" else (4, np.float32)
+
+    def make(name):
+        k, dt = kind(name)
+        return np.zeros((h, w) if k == 1 else (h, w, 4), dt)
+
+    def check(buf, name):
+        k, dt = kind(name)
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < w * h * k:
+            raise L.LrtError(L.LRT_E_INVALID,
+                             f"{name} must be a C-contiguous {np.dtype(dt).name} array of >= {w * h * k} elements")
+
+    return _gbuffer_chain_motion_call(lambda *a: L.lib().lrt_gbuffer_chain_motion_host(ctypes.byref(d), *a),
+                                      first_motion, out, dict(motion=motion, status=status), make,
+                                      lambda b: b.ctypes.data, check, spheres, prev_spheres, ())
+
+
+def gbuffer_chain_motion_tensor(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera],
+                                first_motion, spheres=None, prev_spheres=None, motion: bool = True,
+                                status: bool = True, out: Optional[dict] = None, stream=None, **params) -> dict:
+    """gbuffer_chain_motion_host on cuda tensors (lrt_gbuffer_chain_motion_device): asynchronous on
+    `stream` (a torch.cuda.Stream, default: current) and ordered only against it; the sphere arrays are
+    read before it returns. "status" is an int32 tensor, "motion" float32, on first_motion's device."""
+    import torch
+
+    w, h = int(width), int(height)
+    d = gbuffer_chain_motion_desc(w, h, camera, prev_camera, **params)
+    if not isinstance(first_motion, torch.Tensor) or not first_motion.is_cuda:
+        raise L.LrtError(L.LRT_E_INVALID, "first_motion must be a cuda tensor")
+    dev = first_motion.device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+
+    def kind(name):
+        return (1, torch.int32) if name == "status" else (4, torch.float32)
+
+    def make(name):
+        k, dt = kind(name)
+        with torch.cuda.stream(s):
+            return torch.zeros((h, w) if k == 1 else (h, w, 4), dtype=dt, device=dev)
+
+    def check(t, name):
+        k, dt = kind(name)
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()
+                and t.numel() >= w * h * k):
+            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a contiguous cuda {dt} tensor of >= {w * h * k} elements")
+
+    return _gbuffer_chain_motion_call(lambda *a: L.lib().lrt_gbuffer_chain_motion_device(ctypes.byref(d), *a),
+                                      first_motion, out, dict(motion=motion, status=status), make,
+                                      lambda t: t.data_ptr(), check, spheres, prev_spheres,
+                                      (ctypes.c_void_p(s.cuda_stream),))
+
+
 # ---- G-buffer-guided upsampling of a low-resolution frame -----------------------------------
 def upsample_desc(width: int, height: int, low_width: int, low_height: int, **params) -> L.UpsampleDesc:
     """lrt_upsample_default for a width x height frame from a low_width x low_height one, with any of
