@@ -1332,6 +1332,117 @@ int lrt_gbuffer_chain_motion_device(const lrt_gbuffer_chain_motion_desc* desc, c
 int lrt_gbuffer_chain_motion_host(const lrt_gbuffer_chain_motion_desc* desc, const lrt_scene_motion* scene,
                                   const float* first_motion, const lrt_gbuffer_chain_motion* out);
 
+/* ---- adaptive sampling, part a: the per-pixel sample budget -------------------------------------
+ * lrt_sample_budget_* turns a per-pixel noise estimate -- the variance_out of lrt_svgf_filter_*, or
+ * the color_std of the temporal stages with LRT_SB_STD -- into an integer sample count per pixel
+ * under a total budget, for lrt_render_counts_* below. f32 with no contraction, then exact integers:
+ * the counts are pinned exactly to the NumPy restatement (tests/sample_budget_ref.py).
+ *
+ *  1. Weight. V is the plane's rgb (with LRT_SB_STD each channel squared);
+ *     vY = (0.2126f Vr + 0.7152f Vg) + 0.0722f Vb, Y the same expression of the colour's rgb.
+ *     With a colour plane w = sqrtf(vY) / (fmaxf(Y, 0) + luma_floor) (a relative error), without
+ *     w = sqrtf(vY); sqrtf and the division correctly rounded. A w that is not finite or not > 0
+ *     gives q = 0; otherwise q = (uint32)(fminf(w, weight_max) * 65536.0f), truncated. Alphas are
+ *     never read.
+ *  2. count_p = min_count everywhere.
+ *  3. `passes` times: U = {p : count_p < max_count}, E = budget - sum count (int64),
+ *     Q = sum over U of q_p (uint64), m = |U|. E <= 0 or m = 0: the pass changes nothing. Q = 0:
+ *     add_p = E / m for p in U. Otherwise add_p = (uint64)E * q_p / Q (the product is below 2^62).
+ *     count_p = min(max_count, count_p + add_p). sum count <= budget holds after every pass; what a
+ *     clamp at max_count frees in one pass is handed out again in the next.
+ *  4. d_counts receives width * height int32; d_info[0] = sum count, d_info[1] = pass 1's Q.
+ *
+ * The sums are integer atomics (exact, independent of order); each pass reads E, Q and m from device
+ * memory, so there is no host round trip. Limits: a Neyman-style allocation from a NOISY variance
+ * estimate -- a pixel whose few samples happened to agree is starved until min_count samples show
+ * otherwise, so min_count >= 1 and a filtered variance are the intended inputs. Whole frames, the
+ * first device. */
+#define LRT_COUNT_MAX 4096
+#define LRT_SB_STD 1                 /* the input plane holds a standard deviation (color_std), not a variance */
+typedef struct lrt_sample_budget_desc {
+    int32_t width, height;           /* a whole frame */
+    int32_t flags, reserved;         /* LRT_SB_STD | 0 ; 0 */
+    int32_t min_count, max_count;    /* 0 <= min_count <= max_count <= LRT_COUNT_MAX */
+    int32_t passes;                  /* 1..4; default 2 */
+    int32_t reserved2;               /* 0 */
+    int64_t budget;                  /* min_count * width * height <= budget <= 2^31 - 1 */
+    float luma_floor;                /* finite, > 0; default 0.01 */
+    float weight_max;                /* finite, > 0, <= 16384; default 256 */
+} lrt_sample_budget_desc;
+
+/* The defaults for a width x height frame: flags 0, passes 2, luma_floor 0.01, weight_max 256, and
+ * the counts and the budget as given (checked by the call, not here). */
+int lrt_sample_budget_default(int width, int height, int min_count, int max_count, long long budget,
+                              lrt_sample_budget_desc* out);
+
+/* The counts into device buffers. d_variance: width*height RGBA quads; d_color: the same shape, or
+ * NULL; d_counts: width*height int32; d_info: 2 words, or NULL.
+ *
+ * LRT_E_INVALID, before any device use: NULL desc, d_variance or d_counts; sizes < 1 or
+ * width * height > INT_MAX / 4; an unknown flag or a reserved word != 0; min_count, max_count,
+ * passes, budget, luma_floor or weight_max outside the ranges above (a non-finite float included);
+ * d_counts or d_info overlapping an input or each other by address range. Then LRT_E_STATE without
+ * lrt_initialize(); LRT_E_NOMEM if the scratch cannot be had. Asynchronous on `stream` and ordered
+ * only against it; the intermediates live in the stream's scratch. Acts on the first device. */
+int lrt_sample_budget_device(const lrt_sample_budget_desc* desc, const float* d_variance, const float* d_color,
+                             int32_t* d_counts, unsigned long long* d_info, void* stream);
+
+/* Same with HOST buffers: staged through device memory, blocking; counts and info equal
+ * lrt_sample_budget_device's exactly. */
+int lrt_sample_budget_host(const lrt_sample_budget_desc* desc, const float* variance, const float* color,
+                           int32_t* counts, unsigned long long* info);
+
+/* ---- adaptive sampling, part b: a render that honours a per-pixel count plane --------------------
+ * lrt_render_counts_* renders the window of an ordinary lrt_render_desc (window, row map, frame0,
+ * max_depth and camera honoured; flags must be LRT_F_NONE) with a sample count of its own per pixel.
+ *
+ *   c_p = min(max(counts[p], 0), desc->frames): frames is the per-pixel cap. Pixels are enumerated
+ *   in local row-major order, o_p = sum of c_q over q < p. Pixel p is RENDERED iff c_p > 0 and
+ *   o_p + c_p <= capacity; a pixel with c_p > 0 that does not fit is SKIPPED (the pixels behind it
+ *   keep their offsets). A rendered pixel runs samples frame0 .. frame0 + c_p - 1 with the usual
+ *   seeds, lerped in frame order from the buffer's previous value. Every other pixel keeps all four
+ *   floats; alpha is never written. info[0] = the samples traced, info[1] = the skipped pixels;
+ *   *d_rays grows by the rays of the samples traced.
+ *   LRT_RC_MEAN: after the chain a rendered pixel's rgb is multiplied by
+ *   (float)(frame0 + c_p) / (float)c_p (one IEEE division, three multiplications): rendered into a
+ *   zeroed buffer with frame0 > 0 this is the plain mean of the pixel's fresh samples, the per-pixel
+ *   form of cur_scale; the temporal stages then run with cur_scale = 1.
+ *
+ * Two identities hold bit for bit. A: a rendered pixel equals the same pixel of lrt_render_device
+ * with frames = c_p, everything else equal (whichever kernel that call picks). B: with
+ * counts == frames everywhere and enough capacity, buffer and ray count equal lrt_render_device's.
+ *
+ * Three stages on the stream: an exclusive scan of the clamped counts, a trace kernel over the
+ * compacted sample list (64 consecutive samples are neighbouring pixels of a row; one colour slot of
+ * 16 B per sample), and a merge with one thread per pixel. Scenes of up to 16 spheres are scanned,
+ * larger ones go through the uniform grid, as lrt_gbuffer_chain_* decides; every accelerator gives
+ * the same bits. Limits: the first device; no lrt_features (guides come from lrt_gbuffer_*); no
+ * row-shard exchange into a frame; the scratch holds min(capacity, pixels * frames) slots. */
+#define LRT_RC_MEAN 1
+typedef struct lrt_render_counts {
+    const int32_t* counts;           /* row_count * x_count, the backbuffer's local shape */
+    int64_t capacity;                /* 1 .. 2^27: the most samples the call may trace (sizes its scratch) */
+    int32_t flags, reserved;         /* LRT_RC_MEAN | 0 ; 0 */
+    unsigned long long* info;        /* optional, 2 words written: samples traced, pixels skipped */
+} lrt_render_counts;
+
+/* The render into device buffers (d_rc itself is host memory; its counts and info are device
+ * pointers).
+ *
+ * LRT_E_INVALID, before any device use: what lrt_render_device rejects (a NULL buffer or ray
+ * counter included); a window of more than INT_MAX / 4 pixels; NULL d_rc or counts; capacity outside
+ * 1 .. 2^27; an unknown flag or reserved != 0; desc->flags != 0; counts or info overlapping the
+ * backbuffer or each other by address range. Then LRT_E_STATE without lrt_initialize(); LRT_E_NOMEM
+ * if the scratch cannot be had. Asynchronous on `stream` and ordered only against it, with no host
+ * read-back. Acts on the first device. */
+int lrt_render_counts_device(const lrt_render_desc* desc, const lrt_render_counts* d_rc, float* d_backbuffer,
+                             unsigned long long* d_rays, void* stream);
+
+/* Same with HOST buffers (rc->counts, rc->info and backbuffer in host memory): staged through
+ * device memory, blocking; *out_rays receives the rays of this call. Bit for bit the device form. */
+int lrt_render_counts_host(const lrt_render_desc* desc, const lrt_render_counts* rc, float* backbuffer,
+                           long long* out_rays);
+
 #ifdef __cplusplus
 }
 #endif

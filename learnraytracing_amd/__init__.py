@@ -22,7 +22,9 @@ from .renderer import (DrawTest, InitializeDevices, InitializeTest, Job, Shutdow
                        upsample_desc, upsample_host, upsample_tensor,
                        TemporalUpsampler, jitter_camera, jitter_phases, temporal_upsample_desc,
                        temporal_upsample_host, temporal_upsample_tensor,
-                       temporal_rectify_desc, temporal_rectify_host, temporal_rectify_tensor)
+                       temporal_rectify_desc, temporal_rectify_host, temporal_rectify_tensor,
+                       sample_budget_desc, sample_budget_host, sample_budget_tensor,
+                       render_counts_host, render_counts_tensor)
 from .scene import default_scene, random_scene  # noqa: F401
 
 __version__ = "0.4.0"

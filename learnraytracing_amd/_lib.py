@@ -281,6 +281,30 @@ RECTIFY_PARAMS = ("radius", "min_taps", "min_history", "ref_scale", "gamma", "ra
 RECTIFY_INT_PARAMS = ("radius", "min_taps", "min_history")
 
 
+COUNT_MAX = 4096      # LRT_COUNT_MAX
+SB_STD = 1            # lrt_sample_budget_desc.flags: the input plane is a standard deviation
+RC_MEAN = 1           # lrt_render_counts.flags: the per-pixel mean factor
+RC_CAPACITY_MAX = 1 << 27
+
+
+class SampleBudgetDesc(ctypes.Structure):     # lrt_sample_budget_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("min_count", ctypes.c_int32), ("max_count", ctypes.c_int32),
+                ("passes", ctypes.c_int32), ("reserved2", ctypes.c_int32),
+                ("budget", ctypes.c_int64),
+                ("luma_floor", ctypes.c_float), ("weight_max", ctypes.c_float)]
+
+
+SAMPLE_BUDGET_PARAMS = ("flags", "passes", "luma_floor", "weight_max")
+
+
+class RenderCounts(ctypes.Structure):         # lrt_render_counts
+    _fields_ = [("counts", ctypes.c_void_p), ("capacity", ctypes.c_int64),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("info", ctypes.c_void_p)]
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -375,6 +399,12 @@ SIGNATURES = {
                                              _c.POINTER(GbufferChainMotion), _vp]),
     "lrt_gbuffer_chain_motion_host": (_i, [_c.POINTER(GbufferChainMotionDesc), _c.POINTER(SceneMotion), _vp,
                                            _c.POINTER(GbufferChainMotion)]),
+    "lrt_sample_budget_default": (_i, [_i, _i, _i, _i, _c.c_longlong, _c.POINTER(SampleBudgetDesc)]),
+    "lrt_sample_budget_device": (_i, [_c.POINTER(SampleBudgetDesc), _vp, _vp, _vp, _vp, _vp]),
+    "lrt_sample_budget_host": (_i, [_c.POINTER(SampleBudgetDesc), _vp, _vp, _vp, _vp]),
+    "lrt_render_counts_device": (_i, [_c.POINTER(RenderDesc), _c.POINTER(RenderCounts), _vp, _vp, _vp]),
+    "lrt_render_counts_host": (_i, [_c.POINTER(RenderDesc), _c.POINTER(RenderCounts), _vp,
+                                    _c.POINTER(_c.c_longlong)]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

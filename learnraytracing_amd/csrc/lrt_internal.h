@@ -23,6 +23,10 @@
 //   lrt_upsample.hip  G-buffer-guided upsampling of a low-resolution frame (lrt_upsample_*): kernel and entry points
 //   lrt_temporal_upsample.hip  a full-resolution history from jittered low frames (lrt_temporal_upsample_*, lrt_camera_jitter)
 //   lrt_rectify.hip   history rectification (lrt_temporal_rectify_*): the LDS-tiled window kernel and entry points
+//   lrt_sample_budget.hip  the per-pixel sample budget (lrt_sample_budget_*): weight and pass kernels, entry points
+//   lrt_render_counts.hip  the render under a per-pixel count plane (lrt_render_counts_*): scan, merge, entry points
+//   lrt_render_counts.h    its sample-list trace kernel (counts_trace_kernel) and launch
+//   lrt_render_counts_d8/d64  that kernel's instances for depth <= 8 / <= 64
 //   lrt_atrous.h      the lattice tile of the two a-trous kernels (denoise, svgf): geometry, anchor, staging, taps
 //   lrt_diag.hip      host/device diagnostics (BVH/grid statistics, Scatter and libm probes)
 //   lrt_sort.hip      rocPRIM's radix sort (the tile order)
@@ -437,6 +441,8 @@ hipError_t other_stream_busy(hipStream_t s, bool* busy);
 hipError_t launch_merge_samples(const float4* samp, float4* out, const float* lerp, int npix, int frame0, int frames,
                                 size_t stride, const KernelArgs& a, int pix0, hipStream_t s);
 int launch_wavefront(KernelArgs a, bool lds, hipStream_t s);
+// the camera, scene, window, frame range and destination of a launch, from the descriptor and the context
+void kernel_args_window(const lrt_render_desc* d, float* d_buf, unsigned long long* d_rays, KernelArgs& a);
 // colours_out / frame: see the definition
 int render_device(const lrt_render_desc* d, float* d_buf, unsigned long long* d_rays, const lrt_features* feat,
                   hipStream_t s, float4* colours_out = nullptr, float* frame = nullptr);
@@ -630,6 +636,10 @@ int upload_motion(const lrt_scene_motion* sm, hipStream_t s, const char* what, c
 // pipelined host path's colours-only render (one frame lane, sample planes)
 int launch_v0_d8(const KernelArgs& a, bool lds, int xc, int rows, int frames, bool feat, bool colours, hipStream_t s);
 int launch_v0_d64(const KernelArgs& a, bool lds, int xc, int rows, int frames, bool feat, bool colours, hipStream_t s);
+// ---- lrt_render_counts_d8.hip / lrt_render_counts_d64.hip: the sample-list trace stage (lrt_render_counts.h)
+struct CountsArgs;
+int launch_counts_d8(const KernelArgs& a, const CountsArgs& ca, bool lds, hipStream_t s);
+int launch_counts_d64(const KernelArgs& a, const CountsArgs& ca, bool lds, hipStream_t s);
 // ---- lrt_pool_d8.hip / lrt_pool_d64.hip
 int launch_pool_d8(const KernelArgs& a, bool lds, int xc, int rows, int frames, int pix_cap, hipStream_t s);
 int launch_pool_d64(const KernelArgs& a, bool lds, int xc, int rows, int frames, int pix_cap, hipStream_t s);

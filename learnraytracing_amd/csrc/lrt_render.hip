@@ -350,22 +350,9 @@ int launch_wavefront(KernelArgs a, bool lds, hipStream_t s) {
 }
 
 
-// colours_out (render_host's pipeline): no lerp -- frame f's sample colours go to plane
-// f - frame0 of colours_out (x_count * row_count float4 each) and d_buf is not touched.
-// frame (lrt_render_device_to_frame): every finished pixel is stored there too, at its global
-// row -- the whole width x height RGBA frame, possibly another device's memory.
-int render_device(const lrt_render_desc* d, float* d_buf, unsigned long long* d_rays, const lrt_features* feat,
-                  hipStream_t s, float4* colours_out, float* frame) {
-    int rc = validate(d);
-    if (rc) return rc;
-    if (!ctx().ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
-    if (!d_buf || !d_rays) return fail(LRT_E_INVALID, "device buffer / ray counter is NULL");
-    constexpr int kKnownFlags = LRT_F_SCENE_GLOBAL | LRT_F_SIMPLE | LRT_F_NO_BVH | LRT_F_NO_DOUBLE_LIGHT |
-                                LRT_F_WAVEFRONT | LRT_F_POOL | LRT_F_BVH | LRT_F_GRID;
-    if (d->flags & ~kKnownFlags)   // (every path, the colours-only one too; 4/8/16/128: removed kernels)
-        return fail(LRT_E_INVALID, "unknown LRT_F_* flag (the v1/v2/v3 kernels were removed: the default picks v0 or v5)");
-    if (d->x_count == 0 || d->row_count == 0 || d->frames == 0) return LRT_OK;
-    KernelArgs a;
+// What every render launch takes from the descriptor and the context: the camera, the scene, the
+// window and its row map, the frame range, the destination (render_device and lrt_render_counts_*).
+void kernel_args_window(const lrt_render_desc* d, float* d_buf, unsigned long long* d_rays, KernelArgs& a) {
     const lrt_camera& c = d->camera;
     a.cam.origin = f3(c.origin.x, c.origin.y, c.origin.z);
     a.cam.a = f3(c.a.x, c.a.y, c.a.z);
@@ -396,6 +383,25 @@ int render_device(const lrt_render_desc* d, float* d_buf, unsigned long long* d_
     a.out = reinterpret_cast<float4*>(d_buf);
     a.rays = d_rays;
     a.ndl = (d->flags & LRT_F_NO_DOUBLE_LIGHT) ? 1 : 0;
+}
+
+// colours_out (render_host's pipeline): no lerp -- frame f's sample colours go to plane
+// f - frame0 of colours_out (x_count * row_count float4 each) and d_buf is not touched.
+// frame (lrt_render_device_to_frame): every finished pixel is stored there too, at its global
+// row -- the whole width x height RGBA frame, possibly another device's memory.
+int render_device(const lrt_render_desc* d, float* d_buf, unsigned long long* d_rays, const lrt_features* feat,
+                  hipStream_t s, float4* colours_out, float* frame) {
+    int rc = validate(d);
+    if (rc) return rc;
+    if (!ctx().ready) return fail(LRT_E_STATE, "lrt_initialize() has not been called");
+    if (!d_buf || !d_rays) return fail(LRT_E_INVALID, "device buffer / ray counter is NULL");
+    constexpr int kKnownFlags = LRT_F_SCENE_GLOBAL | LRT_F_SIMPLE | LRT_F_NO_BVH | LRT_F_NO_DOUBLE_LIGHT |
+                                LRT_F_WAVEFRONT | LRT_F_POOL | LRT_F_BVH | LRT_F_GRID;
+    if (d->flags & ~kKnownFlags)   // (every path, the colours-only one too; 4/8/16/128: removed kernels)
+        return fail(LRT_E_INVALID, "unknown LRT_F_* flag (the v1/v2/v3 kernels were removed: the default picks v0 or v5)");
+    if (d->x_count == 0 || d->row_count == 0 || d->frames == 0) return LRT_OK;
+    KernelArgs a;
+    kernel_args_window(d, d_buf, d_rays, a);
     bool want_feat = false;
     {
         float* const fp[6] = {feat ? feat->normal : nullptr,    feat ? feat->world_pos : nullptr,

@@ -1814,6 +1814,143 @@ class TemporalUpsampler:
         return {k: self._states[self._cur][k] for k in L.TEMPORAL_GBUFFER_STATE_NAMES}
 
 
+# ---- adaptive sampling: the per-pixel sample budget and the render that honours it ------------
+def sample_budget_desc(width: int, height: int, min_count: int, max_count: int, budget: int,
+                       **params) -> L.SampleBudgetDesc:
+    """lrt_sample_budget_default for a width x height frame, with any of flags (L.SB_STD), passes,
+    luma_floor, weight_max overridden."""
+    d = L.SampleBudgetDesc()
+    L.check(L.lib().lrt_sample_budget_default(int(width), int(height), int(min_count), int(max_count), int(budget),
+                                              ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.SAMPLE_BUDGET_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown sample budget parameter {name!r}")
+        setattr(d, name, int(v) if name in ("flags", "passes") else float(v))
+    return d
+
+
+def sample_budget_host(variance: np.ndarray, min_count: int, max_count: int, budget: int,
+                       color: Optional[np.ndarray] = None, counts: Optional[np.ndarray] = None, **params):
+    """Per-pixel sample counts from a noise plane (lrt_sample_budget_host). variance: float32
+    [height, width, 4] (or flat with width=, height=), the variance_out of svgf_filter_*, or a
+    color_std with flags=L.SB_STD; color: the same shape, or None (absolute instead of relative
+    error); counts: int32 of >= width * height, default a new [height, width] array. params: flags,
+    passes, luma_floor, weight_max. Returns (counts, info) with info = (sum of the counts, the first
+    pass's weight sum)."""
+    params = dict(params)
+    w, h = _frame_size(variance, params)
+    d = sample_budget_desc(w, h, min_count, max_count, budget, **params)
+    _check_host_buffer(variance, w * h * 4)
+    if color is not None:
+        _check_host_buffer(color, w * h * 4)
+    if counts is None:
+        counts = np.zeros((h, w), np.int32)
+    _check_host_counts(counts, w * h)
+    info = np.zeros(2, np.uint64)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
+    L.check(L.lib().lrt_sample_budget_host(ctypes.byref(d), ptr(variance), ptr(color), ptr(counts), ptr(info)))
+    return counts, (int(info[0]), int(info[1]))
+
+
+def sample_budget_tensor(variance, min_count: int, max_count: int, budget: int, color=None, counts=None, info=None,
+                         stream=None, **params):
+    """sample_budget_host on cuda tensors (lrt_sample_budget_device): asynchronous on `stream` (a
+    torch.cuda.Stream, default: current) and ordered only against it; nothing visits the host.
+    variance, color: float32; counts: int32 of >= width * height (default a new [height, width]
+    tensor); info: int64 of >= 2, or None. Returns counts."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(variance, params)
+    d = sample_budget_desc(w, h, min_count, max_count, budget, **params)
+    n = w * h * 4
+    if not getattr(variance, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"variance must be a contiguous cuda float32 tensor of >= {n} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(variance.device)
+
+    def ok(t, dtype, count):
+        return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == variance.device and t.dtype == dtype
+                and t.is_contiguous() and t.numel() >= count)
+
+    if counts is None:
+        with torch.cuda.stream(s):
+            counts = torch.zeros((h, w), dtype=torch.int32, device=variance.device)
+    for what, t, dtype, count in (("variance", variance, torch.float32, n), ("color", color, torch.float32, n),
+                                  ("counts", counts, torch.int32, w * h), ("info", info, torch.int64, 2)):
+        if not (ok(t, dtype, count) or (t is None and what in ("color", "info"))):
+            kind = str(dtype).replace("torch.", "")
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {kind} tensor of >= {count} elements")
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    L.check(L.lib().lrt_sample_budget_device(ctypes.byref(d), ptr(variance), ptr(color), ptr(counts), ptr(info),
+                                             ctypes.c_void_p(s.cuda_stream)))
+    return counts
+
+
+def _render_counts(d: L.RenderDesc, counts_ptr, capacity, mean: bool, info_ptr, total_cap: int) -> L.RenderCounts:
+    rc = L.RenderCounts()
+    rc.counts = counts_ptr
+    # default: room for every sample the plane can ask for (frames per pixel), within the ABI's range
+    rc.capacity = int(capacity) if capacity is not None else max(1, min(total_cap, L.RC_CAPACITY_MAX))
+    rc.flags = L.RC_MEAN if mean else 0
+    rc.info = info_ptr
+    return rc
+
+
+def render_counts_host(job: Job, backbuffer: np.ndarray, counts: np.ndarray, capacity: Optional[int] = None,
+                       mean: bool = False):
+    """Render `job` with a sample count of its own per pixel (lrt_render_counts_host): counts is an
+    int32 array of row_count * x_count (the backbuffer's local shape), clamped to 0 .. job.frames;
+    capacity: the most samples the call may trace (default: pixels * frames, 2^27 at most) -- a pixel
+    whose samples do not fit is skipped; mean: LRT_RC_MEAN. Pixels with no samples keep their
+    values. Returns (rays, info) with info = (samples traced, pixels skipped)."""
+    d = job.desc()
+    npix = d.row_count * d.x_count
+    _check_host_buffer(backbuffer, npix * 4)
+    _check_host_counts(counts, npix, exact=True)
+    info = np.zeros(2, np.uint64)
+    rc = _render_counts(d, counts.ctypes.data, capacity, mean, info.ctypes.data, npix * d.frames)
+    rays = ctypes.c_longlong(0)
+    L.check(L.lib().lrt_render_counts_host(ctypes.byref(d), ctypes.byref(rc),
+                                           backbuffer.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rays)))
+    return rays.value, (int(info[0]), int(info[1]))
+
+
+def render_counts_tensor(job: Job, buf, rays, counts, capacity: Optional[int], mean: bool = False, info=None,
+                         stream=None) -> None:
+    """torch front end of lrt_render_counts_device: buf and rays as render_tensor takes them, counts
+    a cuda int32 tensor of row_count * x_count elements, capacity as render_counts_host (it sizes the
+    call's scratch; None: pixels * frames), info a cuda int64 tensor of >= 2 elements or None.
+    Asynchronous on `stream` (default: current)."""
+    import torch
+
+    d = job.desc()
+    npix = d.row_count * d.x_count
+    need = npix * 4
+    if not (getattr(buf, "is_cuda", False) and buf.dtype == torch.float32 and buf.is_contiguous()
+            and buf.numel() >= need):
+        raise L.LrtError(L.LRT_E_INVALID, f"buf must be a contiguous cuda float32 tensor of >= {need} elements")
+    if not (getattr(rays, "is_cuda", False) and rays.dtype == torch.int64 and rays.numel() >= 1):
+        raise L.LrtError(L.LRT_E_INVALID, "rays must be a cuda int64 tensor")
+    if not (getattr(counts, "is_cuda", False) and counts.device == buf.device and counts.dtype == torch.int32
+            and counts.is_contiguous() and counts.numel() == npix):
+        raise L.LrtError(L.LRT_E_INVALID, f"counts must be a contiguous cuda int32 tensor of {npix} elements")
+    if info is not None and not (getattr(info, "is_cuda", False) and info.device == buf.device
+                                 and info.dtype == torch.int64 and info.is_contiguous() and info.numel() >= 2):
+        raise L.LrtError(L.LRT_E_INVALID, "info must be a contiguous cuda int64 tensor of >= 2 elements")
+    s = stream if stream is not None else torch.cuda.current_stream(buf.device)
+    rc = _render_counts(d, counts.data_ptr(), capacity, mean, info.data_ptr() if info is not None else None,
+                        npix * d.frames)
+    L.check(L.lib().lrt_render_counts_device(ctypes.byref(d), ctypes.byref(rc), ctypes.c_void_p(buf.data_ptr()),
+                                             ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
+
+
+def _check_host_counts(buf, n: int, exact: bool = False) -> None:
+    if not (isinstance(buf, np.ndarray) and buf.dtype == np.int32 and buf.flags.c_contiguous
+            and (buf.size == n if exact else buf.size >= n)):
+        raise L.LrtError(L.LRT_E_INVALID,
+                         f"counts must be a C-contiguous int32 array of {'' if exact else '>= '}{n} elements")
+
+
 def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
     """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
     import torch
