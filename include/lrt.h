@@ -1443,6 +1443,82 @@ int lrt_render_counts_device(const lrt_render_desc* desc, const lrt_render_count
 int lrt_render_counts_host(const lrt_render_desc* desc, const lrt_render_counts* rc, float* backbuffer,
                            long long* out_rays);
 
+/* ---- firefly suppression: a rank-order clamp ahead of the temporal stages ------------- */
+
+/* A renderer that samples the light explicitly leaves isolated pixels tens of times brighter than
+ * their surroundings. Blended into a history such a spike stays for 1 / alpha_min frames, and
+ * lrt_temporal_rectify_* cannot remove it, because the frame is its reference. This stage is the
+ * one that ReLAX / ReBLUR anti-firefly, the RCRS filter and SVGF's pre-pass share: each pixel's
+ * luminance is clamped against the `rank`-th largest luminance among its neighbours of the same id.
+ * It runs on the current frame's colour, before lrt_temporal_accumulate_gbuffer_*. Comparisons plus
+ * a handful of rounded f32 operations, no contraction: every output is pinned bit for bit to the
+ * NumPy restatement (tests/firefly_ref.py).
+ *
+ * Buffers. in: a whole frame of RGBA f32 quads. id: the int32 plane of lrt_gbuffer_* or the chain's
+ * key, or NULL: every in-image tap then matches.
+ *
+ * Y(c) = (0.2126f c.x + 0.7152f c.y) + 0.0722f c.z, lrt_sample_budget_*'s expression. Per pixel p,
+ * with c = in(p).rgb:
+ *  1. Window. q = p + (dx, dy), |dx|, |dy| <= radius, the centre excluded. A tap counts iff it lies
+ *     inside the image, id(q) = id(p) and Y(q) is finite; a miss matches a miss, and no id is ever
+ *     used as an index. A tap that does not count is kept out by a select: a non-finite neighbour
+ *     never reaches p. m is the count of counting taps.
+ *  2. Support. A pixel with m < min_taps passes through bit for bit, whatever it contains (a
+ *     non-finite value included); its class is 2.
+ *  3. Threshold. Yk is the rank-th largest Y(q) over the counting taps as a multiset (rank 1: the
+ *     maximum; only the value is used, so ties need no rule). T = gain * fmaxf(Yk, 0) + floor: one
+ *     multiplication and one addition, two roundings. floor > 0 makes T positive and the sign of a
+ *     zero Yk irrelevant.
+ *  4. Clamp. Y(c) finite and Y(c) > T, strictly: s = T / Y(c) (IEEE division), c' = s c per
+ *     channel, class 1. Y(c) not finite (a non-finite channel, or a sum that overflows):
+ *     c' = (T, T, T), class 3. Otherwise c' = c bit for bit, class 0.
+ *  5. Outputs. out(p) = c' with in(p)'s alpha bits. excess_out(p), if given, is (c - c', 0) for
+ *     class 1 and four zeros otherwise: a caller that wants the energy back can blur it and add it.
+ *     class_out, if given, is an int32 per pixel. info, if given, is two uint32: the pixels of class
+ *     1 and the pixels of class 3; the call zeroes it on the stream and the integers are exact.
+ *     Nothing else is written.
+ *
+ * Limits: the clamp loses energy; energy is not conserved unless the caller re-adds excess_out. A
+ * legitimately bright feature smaller than `rank` pixels of its own id (a light seen as one pixel)
+ * is dimmed. The threshold comes from one noisy frame. A non-finite pixel without support passes
+ * through. Whole frames only, the first device. */
+#define LRT_FIREFLY_MAX_RADIUS 2
+typedef struct lrt_firefly_desc {      /* 48 bytes */
+    int32_t width, height;             /* a whole frame */
+    int32_t radius;                    /* 1..LRT_FIREFLY_MAX_RADIUS: the window is (2 radius + 1)^2 - 1 taps */
+    int32_t rank;                      /* 1..4 */
+    int32_t min_taps;                  /* rank..(2 radius + 1)^2 - 1: the rank-th tap exists on a supported pixel */
+    int32_t flags;                     /* 0 */
+    float gain;                        /* finite, > 0 */
+    float floor;                       /* finite, > 0, in the buffer's own units */
+    int32_t reserved[4];               /* 0 */
+} lrt_firefly_desc;
+
+/* The defaults: radius 1, rank 2, min_taps 3, gain 2, floor 0.01. Choices in the range the
+ * techniques named above use, not values tuned here: rank 2 lets a pair of adjacent spikes be
+ * caught; at gain 1 a centre that is merely the largest of nine i.i.d. values would already be
+ * clamped. */
+int lrt_firefly_default(int width, int height, lrt_firefly_desc* out);
+
+/* One call on device buffers. d_id, d_excess, d_class and d_info may be NULL.
+ *
+ * Aliasing: no output may overlap an input or another output, by address range (the id and class
+ * planes are width * height * 4 bytes, info 8 bytes, the others 16 bytes per pixel). In place is
+ * not allowed, since neighbours are read.
+ *
+ * LRT_E_INVALID, before any device use: NULL desc, d_in or d_out; sizes < 1 or width * height >
+ * INT_MAX / 4; radius outside 1..LRT_FIREFLY_MAX_RADIUS; rank outside 1..4; min_taps outside
+ * rank..(2 radius + 1)^2 - 1; flags or reserved != 0; gain or floor not finite or <= 0; any overlap
+ * named above. Then LRT_E_STATE without lrt_initialize(). Asynchronous on `stream` and ordered only
+ * against it, with no host round trip and no scratch. Acts on the first device. */
+int lrt_firefly_device(const lrt_firefly_desc* desc, const float* d_in, const int32_t* d_id, float* d_out,
+                       float* d_excess, int32_t* d_class, uint32_t* d_info, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; every output equals
+ * lrt_firefly_device's bit for bit. */
+int lrt_firefly_host(const lrt_firefly_desc* desc, const float* in, const int32_t* id, float* out,
+                     float* excess_out, int32_t* class_out, uint32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

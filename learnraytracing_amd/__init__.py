@@ -24,7 +24,8 @@ from .renderer import (DrawTest, InitializeDevices, InitializeTest, Job, Shutdow
                        temporal_upsample_host, temporal_upsample_tensor,
                        temporal_rectify_desc, temporal_rectify_host, temporal_rectify_tensor,
                        sample_budget_desc, sample_budget_host, sample_budget_tensor,
-                       render_counts_host, render_counts_tensor)
+                       render_counts_host, render_counts_tensor,
+                       firefly_desc, firefly_host, firefly_tensor)
 from .scene import default_scene, random_scene  # noqa: F401
 
 __version__ = "0.4.0"

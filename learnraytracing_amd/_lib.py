@@ -305,6 +305,22 @@ class RenderCounts(ctypes.Structure):         # lrt_render_counts
                 ("info", ctypes.c_void_p)]
 
 
+FIREFLY_MAX_RADIUS = 2        # LRT_FIREFLY_MAX_RADIUS
+FIREFLY_MAX_RANK = 4
+
+
+class FireflyDesc(ctypes.Structure):          # lrt_firefly_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("radius", ctypes.c_int32), ("rank", ctypes.c_int32),
+                ("min_taps", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("gain", ctypes.c_float), ("floor", ctypes.c_float),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+FIREFLY_PARAMS = ("radius", "rank", "min_taps", "gain", "floor")
+FIREFLY_INT_PARAMS = ("radius", "rank", "min_taps")
+
+
 _c = ctypes
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -405,6 +421,9 @@ SIGNATURES = {
     "lrt_render_counts_device": (_i, [_c.POINTER(RenderDesc), _c.POINTER(RenderCounts), _vp, _vp, _vp]),
     "lrt_render_counts_host": (_i, [_c.POINTER(RenderDesc), _c.POINTER(RenderCounts), _vp,
                                     _c.POINTER(_c.c_longlong)]),
+    "lrt_firefly_default": (_i, [_i, _i, _c.POINTER(FireflyDesc)]),
+    "lrt_firefly_device": (_i, [_c.POINTER(FireflyDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lrt_firefly_host": (_i, [_c.POINTER(FireflyDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

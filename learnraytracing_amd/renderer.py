@@ -828,6 +828,7 @@ class TemporalAccumulator:
         self._spheres = None     # its scene, if it was given one
         self._prev_g = None      # the last step_gbuffer's normal and id tensors (None: no history for step_gbuffer())
         self._planes = [None, None]   # gbuffer_planes()'s two sets, allocated on first use
+        self._firefly = None          # step_gbuffer(firefly=...)'s filtered frame, allocated on first use
 
     def reset(self) -> None:
         """Drop the history: the next step or step_gbuffer starts over (a new scene, a camera cut)."""
@@ -875,7 +876,7 @@ class TemporalAccumulator:
         return nxt["color"], {k: nxt[k] for k in L.GUIDE_NAMES if k in out}
 
     def step_gbuffer(self, color, gbuffer: dict, cur_scale: float = 1.0, stream=None, rectify: Optional[dict] = None,
-                     **params):
+                     firefly: Optional[dict] = None, **params):
         """One accumulation step driven by the G-buffer (temporal_accumulate_gbuffer_tensor) of the
         frame `color` with its planes {"normal", "motion", "id"[, ...]} as gbuffer_tensor(id=True,
         motion=True) fills them at guide_scale 1: no camera and no scene. Returns (color,
@@ -889,9 +890,17 @@ class TemporalAccumulator:
         min_history. rectify: None, or a dict of temporal_rectify_tensor's parameters (possibly empty):
         the step is then followed on the same stream by temporal_rectify_tensor in place on the state
         just written, with `color` as the reference, gbuffer's id, ref_scale = cur_scale and the
-        step's own min_history and short_std (unless the dict sets them); color_std is refreshed."""
+        step's own min_history and short_std (unless the dict sets them); color_std is refreshed.
+        firefly: None, or a dict of firefly_tensor's parameters (possibly empty): `color` is then first
+        filtered by firefly_tensor with gbuffer's id, on the same stream, into a scratch frame the
+        accumulator owns, and the step (and its rectify, as the reference) takes that frame instead;
+        `color` itself is left as it is."""
         if not isinstance(gbuffer, dict) or any(n not in gbuffer for n in L.TEMPORAL_GBUFFER_CUR_NAMES):
             raise L.LrtError(L.LRT_E_INVALID, "gbuffer must hold normal, motion and id")
+        if firefly is not None:
+            if not isinstance(firefly, dict):
+                raise L.LrtError(L.LRT_E_INVALID, "firefly must be None or a dict of firefly_tensor's parameters")
+            firefly_desc(self.width, self.height, **firefly)         # an unknown name raises before the step runs
         rp = None
         if rectify is not None:
             if not isinstance(rectify, dict):
@@ -906,6 +915,13 @@ class TemporalAccumulator:
         nxt = self._states[1 - self._cur]
         out = {k: nxt[k] for k in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
         prev = self._states[self._cur] if self._prev_g is not None else None
+        if firefly is not None:
+            if self._firefly is None:
+                import torch
+                # (every quad is written by the pass: uninitialised, so that no fill runs on another stream)
+                self._firefly = torch.empty((self.height, self.width, 4), device=self.device)
+            color = firefly_tensor(color, gbuffer["id"], out=self._firefly, stream=stream, width=self.width,
+                                   height=self.height, **firefly)["out"]
         temporal_accumulate_gbuffer_tensor(color, gbuffer, self._prev_g, prev, out=out, stream=stream,
                                            width=self.width, height=self.height, cur_scale=cur_scale, **params)
         if rp is not None:
@@ -1942,6 +1958,94 @@ def render_counts_tensor(job: Job, buf, rays, counts, capacity: Optional[int], m
                         npix * d.frames)
     L.check(L.lib().lrt_render_counts_device(ctypes.byref(d), ctypes.byref(rc), ctypes.c_void_p(buf.data_ptr()),
                                              ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
+
+
+# ---- firefly suppression ---------------------------------------------------------------------
+def firefly_desc(width: int, height: int, **params) -> L.FireflyDesc:
+    """lrt_firefly_default for a width x height frame, with any of radius, rank, min_taps, gain,
+    floor overridden."""
+    d = L.FireflyDesc()
+    L.check(L.lib().lrt_firefly_default(int(width), int(height), ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.FIREFLY_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown firefly parameter {name!r}")
+        setattr(d, name, int(v) if name in L.FIREFLY_INT_PARAMS else float(v))
+    return d
+
+
+def _firefly_call(entry, color, ids, out, excess_out, class_out, info, check, ptr, make, extra) -> dict:
+    """The argument marshalling the host and tensor front ends share: check(buf, what, kind)
+    validates a buffer ("quad": float32 quads, "word": int32 per pixel, "info": two 32-bit words),
+    ptr(buf) is its address, make(kind) a new zeroed buffer. An optional output given as True is
+    allocated. Returns {"out"[, "excess"][, "class"][, "info"]}."""
+    check(color, "color", "quad")
+    if ids is not None:
+        check(ids, "id", "word")
+    res = {"out": make("quad") if out is None else out}
+    for name, buf, kind in (("excess", excess_out, "quad"), ("class", class_out, "word"), ("info", info, "info")):
+        if buf is not None and buf is not False:
+            res[name] = make(kind) if buf is True else buf
+    for name, kind in (("out", "quad"), ("excess", "quad"), ("class", "word"), ("info", "info")):
+        if name in res:
+            check(res[name], name if name == "out" or name == "info" else f"{name}_out", kind)
+    p = lambda b: ctypes.c_void_p(ptr(b)) if b is not None else None   # noqa: E731
+    L.check(entry(p(color), p(ids), p(res["out"]), p(res.get("excess")), p(res.get("class")), p(res.get("info")), *extra))
+    return res
+
+
+def firefly_host(color: np.ndarray, id: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None,
+                 excess_out=None, class_out=None, info=None, **params) -> dict:
+    """Rank-order firefly suppression of a frame, on host buffers (lrt_firefly_host). color: float32
+    [height, width, 4] (or flat with width=, height=), the current frame before the temporal step;
+    id: the G-buffer's int32 [height, width] id plane (or the chain's key), or None: every tap in
+    the image matches. out: float32 quads, default a new array (never color itself: neighbours are
+    read). excess_out (float32 quads: what the clamp took, for a caller that re-adds it), class_out
+    (int32 per pixel: 0 kept, 1 clamped, 2 fewer than min_taps counting taps: passed through, 3 not
+    finite: grey at the threshold) and info (uint32 of >= 2: the pixels of class 1 and of class 3)
+    are written when given; True allocates one. params: radius, rank, min_taps, gain, floor.
+    Returns {"out"[, "excess"][, "class"][, "info"]}."""
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = firefly_desc(w, h, **params)
+    kinds = {"quad": (w * h * 4, np.float32, (h, w, 4)), "word": (w * h, np.int32, (h, w)), "info": (2, np.uint32, (2,))}
+
+    def check(buf, what, kind):
+        n, dt, _ = kinds[kind]
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
+
+    return _firefly_call(lambda *a: L.lib().lrt_firefly_host(ctypes.byref(d), *a), color, id, out, excess_out, class_out,
+                         info, check, lambda b: b.ctypes.data, lambda kind: np.zeros(kinds[kind][2], kinds[kind][1]), ())
+
+
+def firefly_tensor(color, id=None, out=None, excess_out=None, class_out=None, info=None, stream=None, **params) -> dict:
+    """firefly_host on cuda tensors (lrt_firefly_device): asynchronous on `stream` (a
+    torch.cuda.Stream, default: current) and ordered only against it; nothing visits the host. id
+    and class_out are int32 tensors, info an int32 tensor of >= 2 elements (the two counts), the
+    others float32. Returns {"out"[, "excess"][, "class"][, "info"]}."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = firefly_desc(w, h, **params)
+    if not getattr(color, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {w * h * 4} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color.device)
+    kinds = {"quad": (w * h * 4, torch.float32, (h, w, 4)), "word": (w * h, torch.int32, (h, w)),
+             "info": (2, torch.int32, (2,))}
+
+    def check(t, what, kind):
+        n, dt, _ = kinds[kind]
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == dt
+                and t.is_contiguous() and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
+
+    def make(kind):
+        with torch.cuda.stream(s):
+            return torch.zeros(kinds[kind][2], dtype=kinds[kind][1], device=color.device)
+
+    return _firefly_call(lambda *a: L.lib().lrt_firefly_device(ctypes.byref(d), *a), color, id, out, excess_out,
+                         class_out, info, check, lambda t: t.data_ptr(), make, (ctypes.c_void_p(s.cuda_stream),))
 
 
 def _check_host_counts(buf, n: int, exact: bool = False) -> None:
