@@ -1519,6 +1519,74 @@ int lrt_firefly_device(const lrt_firefly_desc* desc, const float* d_in, const in
 int lrt_firefly_host(const lrt_firefly_desc* desc, const float* in, const int32_t* id, float* out,
                      float* excess_out, int32_t* class_out, uint32_t* info);
 
+/* ---- firefly restore: the clamp's excess spread back over its surface ------------------ */
+
+/* lrt_firefly_* removes energy (7 to 8 % of a 4 spp frame's luminance) that no accumulation
+ * returns. This stage spreads the excess of every clamped pixel over that pixel's neighbours of the
+ * same id with a tent kernel, each source normalised so that what it gives away sums to what it
+ * had, and adds the result to a frame. Small-integer weights, one division, one multiplication and
+ * one addition per tap in a fixed order, no contraction: `out` is pinned bit for bit to the NumPy
+ * restatement (tests/firefly_restore_ref.py).
+ *
+ * Buffers. color: a whole frame of RGBA f32 quads, the clamped `out` of lrt_firefly_* or any later
+ * frame of the same size. excess: RGBA f32, the excess_out of lrt_firefly_*; any plane is legal
+ * input. id: int32 or NULL: every tap in the image then matches; a miss matches a miss, and no id
+ * is ever used as an index. out: RGBA f32.
+ *
+ * With R = radius, t(d) = R + 1 - |d| and w(dx, dy) = t(dx) t(dy): small integers, exact in f32.
+ *  1. Source. e(p) = excess(p).xyz if all three channels satisfy |e| <= 0x1p100f, otherwise
+ *     (0, 0, 0): NaN and +-Inf fail the test. A select. The cap keeps every partial sum finite, so
+ *     no NaN is ever made by arithmetic.
+ *  2. Normaliser. W(p) = the sum of w(dx, dy) over dx, dy in -R..R, the centre included, over the
+ *     taps q = p + (dx, dy) that lie in the image with id(q) = id(p): an integer in
+ *     (R + 1)^2..(R + 1)^4, exact in f32 in any order. n(p) = e(p) / (float)W(p), one IEEE division
+ *     per channel.
+ *  3. Gather. Per destination q, acc = (+0, +0, +0); for dy = -R..R ascending and inside it
+ *     dx = -R..R ascending, p = q + (dx, dy): if p lies in the image and id(p) = id(q),
+ *     acc = acc + (float)w(dx, dy) * n(p) per channel, one rounded multiplication and then one
+ *     rounded addition. A tap that does not count is skipped.
+ *  4. Write. Per channel out.c = color.c + acc.c if acc.c != 0 and color.c is finite; otherwise
+ *     out.c keeps color.c's bits. out.w keeps color.w's bits. A pixel that no excess reaches comes
+ *     out bit for bit, -0, NaN payloads and alpha included.
+ *
+ * The id test and the weights are symmetric, so in real arithmetic the sum of out over the frame is
+ * the sum of color plus the sum of e: a source alone on its id gets its own excess back
+ * (W = (R + 1)^2, one tap).
+ *
+ * Limits: energy returns to the surface, not to the pixel it left, so the frame is blurred by what
+ * was clamped; a source whose excess is not finite or above 0x1p100f gives nothing; rounding makes
+ * the conservation first-order exact only ((2R + 1)^2 + 3 roundings of 2^-24 per pixel). Whole
+ * frames only, the first device. */
+#define LRT_FIREFLY_RESTORE_MAX_RADIUS 4
+typedef struct lrt_firefly_restore_desc {   /* 32 bytes */
+    int32_t width, height;             /* a whole frame */
+    int32_t radius;                    /* 1..LRT_FIREFLY_RESTORE_MAX_RADIUS: the tent spans (2 radius + 1)^2 taps */
+    int32_t flags;                     /* 0 */
+    int32_t reserved[4];               /* 0 */
+} lrt_firefly_restore_desc;
+
+/* The default: radius 2. */
+int lrt_firefly_restore_default(int width, int height, lrt_firefly_restore_desc* out);
+
+/* One call on device buffers. d_id may be NULL.
+ *
+ * Aliasing: d_out may be d_color itself (the same pointer: in place; a thread reads only its own
+ * color quad). Any other overlap between d_out and an input, by address range (the id plane is
+ * width * height * 4 bytes, the others 16 bytes per pixel), is refused.
+ *
+ * LRT_E_INVALID, before any device use: NULL desc, d_color, d_excess or d_out; sizes < 1 or
+ * width * height > INT_MAX / 4; radius outside 1..LRT_FIREFLY_RESTORE_MAX_RADIUS; flags or reserved
+ * != 0; any overlap named above. Then LRT_E_STATE without lrt_initialize(). Asynchronous on
+ * `stream` and ordered only against it, with no host round trip, no scratch and no atomics. Acts on
+ * the first device. */
+int lrt_firefly_restore_device(const lrt_firefly_restore_desc* desc, const float* d_color, const float* d_excess,
+                               const int32_t* d_id, float* d_out, void* stream);
+
+/* Same on HOST buffers: staged through device memory, blocking; out equals
+ * lrt_firefly_restore_device's bit for bit. out may be color itself. */
+int lrt_firefly_restore_host(const lrt_firefly_restore_desc* desc, const float* color, const float* excess,
+                             const int32_t* id, float* out);
+
 #ifdef __cplusplus
 }
 #endif

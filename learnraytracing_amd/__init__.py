@@ -25,7 +25,8 @@ from .renderer import (DrawTest, InitializeDevices, InitializeTest, Job, Shutdow
                        temporal_rectify_desc, temporal_rectify_host, temporal_rectify_tensor,
                        sample_budget_desc, sample_budget_host, sample_budget_tensor,
                        render_counts_host, render_counts_tensor,
-                       firefly_desc, firefly_host, firefly_tensor)
+                       firefly_desc, firefly_host, firefly_tensor,
+                       firefly_restore_desc, firefly_restore_host, firefly_restore_tensor)
 from .scene import default_scene, random_scene  # noqa: F401
 
 __version__ = "0.4.0"

@@ -320,6 +320,17 @@ class FireflyDesc(ctypes.Structure):          # lrt_firefly_desc
 FIREFLY_PARAMS = ("radius", "rank", "min_taps", "gain", "floor")
 FIREFLY_INT_PARAMS = ("radius", "rank", "min_taps")
 
+FIREFLY_RESTORE_MAX_RADIUS = 4        # LRT_FIREFLY_RESTORE_MAX_RADIUS
+
+
+class FireflyRestoreDesc(ctypes.Structure):   # lrt_firefly_restore_desc
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("radius", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+FIREFLY_RESTORE_PARAMS = ("radius",)
+
 
 _c = ctypes
 _vp = ctypes.c_void_p
@@ -424,6 +435,9 @@ SIGNATURES = {
     "lrt_firefly_default": (_i, [_i, _i, _c.POINTER(FireflyDesc)]),
     "lrt_firefly_device": (_i, [_c.POINTER(FireflyDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lrt_firefly_host": (_i, [_c.POINTER(FireflyDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lrt_firefly_restore_default": (_i, [_i, _i, _c.POINTER(FireflyRestoreDesc)]),
+    "lrt_firefly_restore_device": (_i, [_c.POINTER(FireflyRestoreDesc), _vp, _vp, _vp, _vp, _vp]),
+    "lrt_firefly_restore_host": (_i, [_c.POINTER(FireflyRestoreDesc), _vp, _vp, _vp, _vp]),
 }
 # include/lrt_diag.h: diagnostics and test hooks, bound when the library exports them (the
 # product path needs none of them; a build without them still loads)

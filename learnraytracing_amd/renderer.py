@@ -829,6 +829,7 @@ class TemporalAccumulator:
         self._prev_g = None      # the last step_gbuffer's normal and id tensors (None: no history for step_gbuffer())
         self._planes = [None, None]   # gbuffer_planes()'s two sets, allocated on first use
         self._firefly = None          # step_gbuffer(firefly=...)'s filtered frame, allocated on first use
+        self._excess = None           # step_gbuffer(firefly_restore=...)'s excess frame, allocated on first use
 
     def reset(self) -> None:
         """Drop the history: the next step or step_gbuffer starts over (a new scene, a camera cut)."""
@@ -876,7 +877,7 @@ class TemporalAccumulator:
         return nxt["color"], {k: nxt[k] for k in L.GUIDE_NAMES if k in out}
 
     def step_gbuffer(self, color, gbuffer: dict, cur_scale: float = 1.0, stream=None, rectify: Optional[dict] = None,
-                     firefly: Optional[dict] = None, **params):
+                     firefly: Optional[dict] = None, firefly_restore: Optional[dict] = None, **params):
         """One accumulation step driven by the G-buffer (temporal_accumulate_gbuffer_tensor) of the
         frame `color` with its planes {"normal", "motion", "id"[, ...]} as gbuffer_tensor(id=True,
         motion=True) fills them at guide_scale 1: no camera and no scene. Returns (color,
@@ -894,13 +895,23 @@ class TemporalAccumulator:
         firefly: None, or a dict of firefly_tensor's parameters (possibly empty): `color` is then first
         filtered by firefly_tensor with gbuffer's id, on the same stream, into a scratch frame the
         accumulator owns, and the step (and its rectify, as the reference) takes that frame instead;
-        `color` itself is left as it is."""
+        `color` itself is left as it is. firefly_restore: None, or a dict of firefly_restore_tensor's
+        parameters (possibly empty); it needs firefly: the firefly call then also writes its excess
+        into a second scratch frame, and firefly_restore_tensor runs in place on the clamped frame with
+        gbuffer's id, on the same stream, ahead of the accumulation."""
         if not isinstance(gbuffer, dict) or any(n not in gbuffer for n in L.TEMPORAL_GBUFFER_CUR_NAMES):
             raise L.LrtError(L.LRT_E_INVALID, "gbuffer must hold normal, motion and id")
         if firefly is not None:
             if not isinstance(firefly, dict):
                 raise L.LrtError(L.LRT_E_INVALID, "firefly must be None or a dict of firefly_tensor's parameters")
             firefly_desc(self.width, self.height, **firefly)         # an unknown name raises before the step runs
+        if firefly_restore is not None:
+            if not isinstance(firefly_restore, dict):
+                raise L.LrtError(L.LRT_E_INVALID,
+                                 "firefly_restore must be None or a dict of firefly_restore_tensor's parameters")
+            if firefly is None:
+                raise L.LrtError(L.LRT_E_INVALID, "firefly_restore needs firefly: the clamp supplies the excess")
+            firefly_restore_desc(self.width, self.height, **firefly_restore)
         rp = None
         if rectify is not None:
             if not isinstance(rectify, dict):
@@ -920,8 +931,15 @@ class TemporalAccumulator:
                 import torch
                 # (every quad is written by the pass: uninitialised, so that no fill runs on another stream)
                 self._firefly = torch.empty((self.height, self.width, 4), device=self.device)
+            if firefly_restore is not None and self._excess is None:
+                import torch
+                self._excess = torch.empty((self.height, self.width, 4), device=self.device)
             color = firefly_tensor(color, gbuffer["id"], out=self._firefly, stream=stream, width=self.width,
-                                   height=self.height, **firefly)["out"]
+                                   height=self.height, excess_out=self._excess if firefly_restore is not None else None,
+                                   **firefly)["out"]
+            if firefly_restore is not None:
+                firefly_restore_tensor(color, self._excess, gbuffer["id"], out=color, stream=stream, width=self.width,
+                                       height=self.height, **firefly_restore)
         temporal_accumulate_gbuffer_tensor(color, gbuffer, self._prev_g, prev, out=out, stream=stream,
                                            width=self.width, height=self.height, cur_scale=cur_scale, **params)
         if rp is not None:
@@ -2046,6 +2064,80 @@ def firefly_tensor(color, id=None, out=None, excess_out=None, class_out=None, in
 
     return _firefly_call(lambda *a: L.lib().lrt_firefly_device(ctypes.byref(d), *a), color, id, out, excess_out,
                          class_out, info, check, lambda t: t.data_ptr(), make, (ctypes.c_void_p(s.cuda_stream),))
+
+
+# ---- firefly restore ---------------------------------------------------------------------------
+def firefly_restore_desc(width: int, height: int, **params) -> L.FireflyRestoreDesc:
+    """lrt_firefly_restore_default for a width x height frame, with radius overridden if given."""
+    d = L.FireflyRestoreDesc()
+    L.check(L.lib().lrt_firefly_restore_default(int(width), int(height), ctypes.byref(d)))
+    for name, v in params.items():
+        if name not in L.FIREFLY_RESTORE_PARAMS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown firefly restore parameter {name!r}")
+        setattr(d, name, int(v))
+    return d
+
+
+def firefly_restore_host(color: np.ndarray, excess: np.ndarray, id: Optional[np.ndarray] = None,
+                         out: Optional[np.ndarray] = None, **params) -> dict:
+    """The firefly clamp's excess spread back over its surface and added to a frame, on host buffers
+    (lrt_firefly_restore_host). color: float32 [height, width, 4] (or flat with width=, height=), the
+    `out` of firefly_host or a later frame of the same size; excess: float32 quads, firefly_host's
+    excess_out; id: the int32 [height, width] plane the clamp ran with, or None: every tap in the
+    image matches. out: float32 quads, default a new array; out=color means in place. params: radius.
+    Returns {"out"}."""
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = firefly_restore_desc(w, h, **params)
+    kinds = {"quad": (w * h * 4, np.float32), "word": (w * h, np.int32)}
+
+    def check(buf, what, kind):
+        n, dt = kinds[kind]
+        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
+
+    check(color, "color", "quad")
+    check(excess, "excess", "quad")
+    if id is not None:
+        check(id, "id", "word")
+    if out is None:
+        out = np.zeros((h, w, 4), np.float32)
+    check(out, "out", "quad")
+    p = lambda b: ctypes.c_void_p(b.ctypes.data) if b is not None else None   # noqa: E731
+    L.check(L.lib().lrt_firefly_restore_host(ctypes.byref(d), p(color), p(excess), p(id), p(out)))
+    return {"out": out}
+
+
+def firefly_restore_tensor(color, excess, id=None, out=None, stream=None, **params) -> dict:
+    """firefly_restore_host on cuda tensors (lrt_firefly_restore_device): asynchronous on `stream` (a
+    torch.cuda.Stream, default: current) and ordered only against it; nothing visits the host. id is
+    an int32 tensor, the others float32; out=color means in place. Returns {"out"}."""
+    import torch
+
+    params = dict(params)
+    w, h = _frame_size(color, params)
+    d = firefly_restore_desc(w, h, **params)
+    if not getattr(color, "is_cuda", False):
+        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {w * h * 4} elements")
+    s = stream if stream is not None else torch.cuda.current_stream(color.device)
+
+    def check(t, what, n, dt):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == dt
+                and t.is_contiguous() and t.numel() >= n):
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
+
+    check(color, "color", w * h * 4, torch.float32)
+    check(excess, "excess", w * h * 4, torch.float32)
+    if id is not None:
+        check(id, "id", w * h, torch.int32)
+    if out is None:
+        with torch.cuda.stream(s):
+            out = torch.zeros((h, w, 4), dtype=torch.float32, device=color.device)
+    check(out, "out", w * h * 4, torch.float32)
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    L.check(L.lib().lrt_firefly_restore_device(ctypes.byref(d), p(color), p(excess), p(id), p(out),
+                                               ctypes.c_void_p(s.cuda_stream)))
+    return {"out": out}
 
 
 def _check_host_counts(buf, n: int, exact: bool = False) -> None:
