@@ -23,6 +23,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from . import _buffers as B
 from . import _lib as L
 
 
@@ -58,7 +59,7 @@ def DrawTest(time: float, frameCount: int, screenWidth: int, screenHeight: int,
     """The reference's DrawTest (parallel.h:8): one progressive frame into the caller's
     float RGBA backbuffer (any host memory; a pageable array is page-locked for the call
     only). Returns the rays counted (outRayCount)."""
-    _check_host_buffer(backbuffer, screenWidth * screenHeight * 4)
+    B.HostBuffers().check(backbuffer, "backbuffer", screenWidth * screenHeight * 4)
     rays = ctypes.c_int(0)
     L.check(L.lib().lrt_draw_test(float(time), int(frameCount), int(screenWidth), int(screenHeight),
                                   backbuffer.ctypes.data_as(ctypes.c_void_p), ctypes.byref(rays)))
@@ -155,7 +156,7 @@ def pinned_backbuffer(n_floats: int) -> np.ndarray:
 def render_host(job: Job, backbuffer: np.ndarray) -> int:
     """Render `job` into a host float32 buffer (row_count*x_count*4). Returns rays."""
     d = job.desc()
-    _check_host_buffer(backbuffer, d.row_count * d.x_count * 4)
+    B.HostBuffers().check(backbuffer, "backbuffer", d.row_count * d.x_count * 4)
     rays = ctypes.c_longlong(0)
     L.check(L.lib().lrt_render_host(ctypes.byref(d), backbuffer.ctypes.data_as(ctypes.c_void_p),
                                     ctypes.byref(rays)))
@@ -169,14 +170,9 @@ def render_host_features(job: Job, backbuffer: np.ndarray, features: dict, max_f
     for frames <= max_frame (< 0: all). Returns rays."""
     d = job.desc()
     n = d.row_count * d.x_count * 4
-    _check_host_buffer(backbuffer, n)
-    f = L.Features()
+    B.HostBuffers().check(backbuffer, "backbuffer", n)
+    f = _features(B.HostBuffers(), features, n, L.FEATURE_NAMES, "feature")
     f.max_frame = int(max_frame)
-    for name, buf in features.items():
-        if name not in L.FEATURE_NAMES:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown feature {name!r}")
-        _check_host_buffer(buf, n)
-        setattr(f, name, buf.ctypes.data)
     rays = ctypes.c_longlong(0)
     L.check(L.lib().lrt_render_host_ex(ctypes.byref(d), backbuffer.ctypes.data_as(ctypes.c_void_p),
                                        ctypes.byref(rays), ctypes.byref(f)))
@@ -297,12 +293,78 @@ def render_tensor_features(job: Job, buf, rays, features: dict, max_frame: int =
         raise L.LrtError(L.LRT_E_INVALID, f"buf must be a contiguous cuda float32 tensor of >= {need} elements")
     if not (rays.is_cuda and rays.dtype == torch.int64 and rays.numel() >= 1):
         raise L.LrtError(L.LRT_E_INVALID, "rays must be a cuda int64 tensor")
-    f = _tensor_features(features, need, L.FEATURE_NAMES, buf.device)
-    f.max_frame = int(max_frame)
     s = stream if stream is not None else torch.cuda.current_stream(buf.device)
+    f = _features(B.TensorBuffers(buf.device, s), features, need, L.FEATURE_NAMES, "feature")
+    f.max_frame = int(max_frame)
     L.check(L.lib().lrt_render_device_ex(ctypes.byref(d), ctypes.c_void_p(buf.data_ptr()),
                                          ctypes.c_void_p(rays.data_ptr()), ctypes.byref(f),
                                          ctypes.c_void_p(s.cuda_stream)))
+
+
+# ---- what the post-process front ends share ------------------------------------------------
+# Each unit below has one body taking a back end of _buffers.py (`bufs`: NumPy arrays -> lrt_*_host,
+# cuda tensors -> lrt_*_device on a stream); its *_host and *_tensor size the frame, fill the desc and
+# construct the back end.
+def _override(d, params: dict, allowed, int_names, what: str):
+    """The desc `d` with the caller's `params` set over its defaults."""
+    for name, v in params.items():
+        if name not in allowed:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown {what} parameter {name!r}")
+        setattr(d, name, int(v) if name in int_names else float(v))
+    return d
+
+
+def _kinds(width: int, height: int, words=("id",), scalars=("depth",)) -> dict:
+    """B.planes of a width x height frame, plus the names of the planes that are not RGBA quads: an
+    int32 word per pixel for those in `words`, a float for those in `scalars`."""
+    k = B.planes(width, height)
+    for name in words:
+        k[name] = k["word"]
+    for name in scalars:
+        k[name] = k["scalar"]
+    return k
+
+
+def _members(bufs, given, struct, kinds: dict, *, known, stored, noun: str, need=(), what: str = ""):
+    """A dict of buffers as the ctypes `struct` of their addresses. `given` (called `what` in messages)
+    must hold the names in `need` and may hold any in `known`, so that a whole G-buffer or a returned
+    state passes as it is; only the members in `stored` are checked, as their plane of _kinds(), and
+    stored."""
+    quad = kinds["quad"]
+    for name in need:
+        if not isinstance(given, dict) or name not in given:
+            raise L.LrtError(L.LRT_E_INVALID, f"{what} lacks {name!r}: it must hold " + " and ".join(need))
+    st = struct()
+    for name, buf in given.items():
+        if name not in known:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown {noun} {name!r}")
+        if name in stored:
+            bufs.check_plane(buf, f"{what} {name}" if what else name, kinds.get(name, quad))
+            setattr(st, name, bufs.address(buf))
+    return st
+
+
+def _features(bufs, given: dict, n: int, known, noun: str, stored=None) -> L.Features:
+    """lrt_features over float32 buffers of >= n elements, keyed by its member names."""
+    every = {"quad": (n, ("float32",), None)}        # (no other kind of plane among the features)
+    return _members(bufs, given, L.Features, every, known=known, stored=known if stored is None else stored, noun=noun)
+
+
+def _color_std(bufs, out: dict, quad):
+    """The address of a state's optional color_std, or None."""
+    if "color_std" not in out:
+        return None
+    bufs.check_plane(out["color_std"], "out color_std", quad)
+    return bufs.ptr(out["color_std"])
+
+
+def _moved(spheres, prev_spheres):
+    """The lrt_scene_motion argument of the units that take a previous scene: None without one."""
+    if prev_spheres is not None:
+        return ctypes.byref(_scene_motion(spheres if spheres is not None else get_scene()[0], prev_spheres))
+    if spheres is not None:
+        raise L.LrtError(L.LRT_E_INVALID, "spheres needs prev_spheres")
+    return None
 
 
 # ---- denoiser ---------------------------------------------------------------------------
@@ -311,11 +373,8 @@ def denoise_desc(width: int, height: int, **params) -> L.DenoiseDesc:
     sigma_normal, sigma_pos, sigma_albedo overridden."""
     d = L.DenoiseDesc()
     L.check(L.lib().lrt_denoise_default(int(width), int(height), ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in ("iterations", "sigma_color", "sigma_normal", "sigma_pos", "sigma_albedo"):
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown denoise parameter {name!r}")
-        setattr(d, name, int(v) if name == "iterations" else float(v))
-    return d
+    return _override(d, params, ("iterations", "sigma_color", "sigma_normal", "sigma_pos", "sigma_albedo"),
+                     ("iterations",), "denoise")
 
 
 def _frame_size(color, params: dict):
@@ -328,6 +387,18 @@ def _frame_size(color, params: dict):
     return int(w), int(h)
 
 
+def _denoise(bufs, d, color, guides, out):
+    n = d.width * d.height * 4
+    bufs.check(color, "color", n)
+    if out is None:
+        out = bufs.copy(color)
+    bufs.check(out, "out", n)
+    f = _features(bufs, guides or {}, n, L.GUIDE_NAMES, "guide")
+    L.check(bufs.entry("denoise")(ctypes.byref(d), bufs.ptr(color), ctypes.byref(f) if guides else None,
+                                  bufs.ptr(out), *bufs.tail))
+    return out
+
+
 def denoise_host(color: np.ndarray, guides: Optional[dict], out: Optional[np.ndarray] = None, **params):
     """Filter a rendered frame with the feature-guided a-trous denoiser (lrt_denoise_host).
     color: float32 [height, width, 4] (or flat with width=, height=); guides: {name: buffer}
@@ -337,49 +408,16 @@ def denoise_host(color: np.ndarray, guides: Optional[dict], out: Optional[np.nda
     iterations, sigma_color, sigma_normal, sigma_pos, sigma_albedo. Returns out."""
     params = dict(params)
     w, h = _frame_size(color, params)
-    d = denoise_desc(w, h, **params)
-    n = w * h * 4
-    _check_host_buffer(color, n)
-    if out is None:
-        out = color.copy()
-    _check_host_buffer(out, n)
-    f = L.Features()
-    for name, buf in (guides or {}).items():
-        if name not in L.GUIDE_NAMES:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown guide {name!r}")
-        _check_host_buffer(buf, n)
-        setattr(f, name, buf.ctypes.data)
-    L.check(L.lib().lrt_denoise_host(ctypes.byref(d), color.ctypes.data_as(ctypes.c_void_p),
-                                     ctypes.byref(f) if guides else None, out.ctypes.data_as(ctypes.c_void_p)))
-    return out
+    return _denoise(B.HostBuffers(), denoise_desc(w, h, **params), color, guides, out)
 
 
 def denoise_tensor(color, guides: Optional[dict], out=None, stream=None, **params):
     """denoise_host on cuda float32 tensors (lrt_denoise_device): asynchronous on `stream` (a
     torch.cuda.Stream, default: current) and ordered only against it. Returns out."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(color, params)
     d = denoise_desc(w, h, **params)
-    n = w * h * 4
-    s = stream if stream is not None else torch.cuda.current_stream(color.device)
-
-    def ok(t):
-        return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n
-
-    if not ok(color):
-        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
-    if out is None:
-        with torch.cuda.stream(s):
-            out = color.clone()
-    if not ok(out):
-        raise L.LrtError(L.LRT_E_INVALID, f"out must be a contiguous cuda float32 tensor of >= {n} elements")
-    f = _tensor_features(guides or {}, n, L.GUIDE_NAMES, color.device)
-    L.check(L.lib().lrt_denoise_device(ctypes.byref(d), ctypes.c_void_p(color.data_ptr()),
-                                       ctypes.byref(f) if guides else None, ctypes.c_void_p(out.data_ptr()),
-                                       ctypes.c_void_p(s.cuda_stream)))
-    return out
+    return _denoise(B.tensor_buffers(color, "color", w * h * 4, stream), d, color, guides, out)
 
 
 # ---- temporal reprojection and accumulation ------------------------------------------------
@@ -394,57 +432,35 @@ def temporal_desc(width: int, height: int, camera: L.Camera, prev_camera: Option
     L.check(L.lib().lrt_temporal_default(int(width), int(height), ctypes.byref(camera),
                                          ctypes.byref(prev_camera) if prev_camera is not None else None,
                                          ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.TEMPORAL_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown temporal parameter {name!r}")
-        setattr(d, name, int(v) if name == "min_history" else float(v))
-    return d
+    return _override(d, params, L.TEMPORAL_PARAMS, ("min_history",), "temporal")
 
 
-def _temporal_call(entry, color, cur, prev, out, n, check, ptr, make, extra):
-    """The argument marshalling the host and tensor front ends share: check(buf, what) validates a
-    buffer of >= n elements, ptr(buf) is its address, make() a zeroed frame. Returns the new state."""
-    check(color, "color")
-    if not isinstance(cur, dict) or "normal" not in cur or "world_pos" not in cur:
-        raise L.LrtError(L.LRT_E_INVALID, "cur must hold normal and world_pos")
-    f = L.Features()
-    for name, buf in cur.items():
-        if name not in L.TEMPORAL_CUR_NAMES:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown feature {name!r}")
-        check(buf, name)
-        setattr(f, name, ptr(buf))
+def _temporal(bufs, unit, head, color, cur, prev, out, motion=()):
+    """The step's marshalling. head: (desc,) or (desc, scene motion), by reference; motion: the moving
+    form's (motion,). Returns the new state."""
+    k = _kinds(head[0].width, head[0].height)
+    quad = k["quad"]
+    for buf in motion:                       # (ahead of color, as the moving form always checked it)
+        if buf is not None:
+            bufs.check_plane(buf, "motion", quad)
+    bufs.check_plane(color, "color", quad)
+    f = _members(bufs, cur, L.Features, k, what="cur", need=("normal", "world_pos"), known=L.TEMPORAL_CUR_NAMES,
+                 stored=L.TEMPORAL_CUR_NAMES, noun="feature")
+    # (a returned state may be passed back as it is: its color_std is not read)
+    known = L.TEMPORAL_STATE_NAMES + ("color_std",)
     ps = None
     if prev is not None:
-        ps = L.TemporalState()
-        for name in L.TEMPORAL_STATE_NAMES[:4]:
-            if name not in prev:
-                raise L.LrtError(L.LRT_E_INVALID, f"prev lacks {name!r}")
-        for name, buf in prev.items():
-            if name == "color_std":      # a returned state may be passed back as it is
-                continue
-            if name not in L.TEMPORAL_STATE_NAMES:
-                raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
-            check(buf, "prev " + name)
-            setattr(ps, name, ptr(buf))
+        ps = _members(bufs, prev, L.TemporalState, k, what="prev", need=L.TEMPORAL_STATE_NAMES[:4], known=known,
+                      stored=L.TEMPORAL_STATE_NAMES, noun="state buffer")
     if out is None:
-        out = {name: make() for name in L.TEMPORAL_STATE_NAMES[:4] + ("color_std",)}
+        out = {name: bufs.new(quad) for name in L.TEMPORAL_STATE_NAMES[:4] + ("color_std",)}
         if "albedo" in cur:
-            out["albedo"] = make()
-    ns = L.TemporalState()
-    std = None
-    for name in L.TEMPORAL_STATE_NAMES[:4]:
-        if name not in out:
-            raise L.LrtError(L.LRT_E_INVALID, f"out lacks {name!r}")
-    for name, buf in out.items():
-        if name not in L.TEMPORAL_STATE_NAMES + ("color_std",):
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
-        check(buf, "out " + name)
-        if name == "color_std":
-            std = ptr(buf)
-        else:
-            setattr(ns, name, ptr(buf))
-    L.check(entry(ctypes.c_void_p(ptr(color)), ctypes.byref(f), ctypes.byref(ps) if ps is not None else None,
-                  ctypes.byref(ns), ctypes.c_void_p(std) if std else None, *extra))
+            out["albedo"] = bufs.new(quad)
+    ns = _members(bufs, out, L.TemporalState, k, what="out", need=L.TEMPORAL_STATE_NAMES[:4], known=known,
+                  stored=L.TEMPORAL_STATE_NAMES, noun="state buffer")
+    L.check(bufs.entry(unit)(*(ctypes.byref(a) for a in head), bufs.ptr(color), ctypes.byref(f),
+                             ctypes.byref(ps) if ps is not None else None, ctypes.byref(ns),
+                             _color_std(bufs, out, quad), *(bufs.ptr(m) for m in motion), *bufs.tail))
     return out
 
 
@@ -461,13 +477,7 @@ def temporal_accumulate_host(color: np.ndarray, cur: dict, prev: Optional[dict],
     params = dict(params)
     w, h = _frame_size(color, params)
     d = temporal_desc(w, h, camera, prev_camera, **params)
-    n = w * h * 4
-
-    def check(buf, what):
-        _check_host_buffer(buf, n)
-
-    return _temporal_call(lambda *a: L.lib().lrt_temporal_accumulate_host(ctypes.byref(d), *a), color, cur, prev,
-                          out, n, check, lambda b: b.ctypes.data, lambda: np.zeros((h, w, 4), np.float32), ())
+    return _temporal(B.HostBuffers(), "temporal_accumulate", (d,), color, cur, prev, out)
 
 
 def temporal_accumulate_tensor(color, cur: dict, prev: Optional[dict], camera: L.Camera,
@@ -476,27 +486,11 @@ def temporal_accumulate_tensor(color, cur: dict, prev: Optional[dict], camera: L
     """temporal_accumulate_host on cuda float32 tensors (lrt_temporal_accumulate_device):
     asynchronous on `stream` (a torch.cuda.Stream, default: current) and ordered only against it.
     Returns the new state."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(color, params)
     d = temporal_desc(w, h, camera, prev_camera, **params)
-    n = w * h * 4
-    if not getattr(color, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color.device)
-
-    def check(t, what):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == torch.float32
-                and t.is_contiguous() and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda float32 tensor of >= {n} elements")
-
-    def make():
-        with torch.cuda.stream(s):
-            return torch.zeros((h, w, 4), device=color.device)
-
-    return _temporal_call(lambda *a: L.lib().lrt_temporal_accumulate_device(ctypes.byref(d), *a), color, cur, prev,
-                          out, n, check, lambda t: t.data_ptr(), make, (ctypes.c_void_p(s.cuda_stream),))
+    bufs = B.tensor_buffers(color, "color", w * h * 4, stream)
+    return _temporal(bufs, "temporal_accumulate", (d,), color, cur, prev, out)
 
 
 def _sphere_array(spheres, what):
@@ -540,17 +534,7 @@ def temporal_accumulate_moving_host(color: np.ndarray, cur: dict, prev: Optional
     w, h = _frame_size(color, params)
     d = temporal_desc(w, h, camera, prev_camera, **params)
     sm = _scene_motion(spheres, prev_spheres)
-    n = w * h * 4
-
-    def check(buf, what):
-        _check_host_buffer(buf, n)
-
-    if motion is not None:
-        check(motion, "motion")
-    mp = ctypes.c_void_p(motion.ctypes.data) if motion is not None else None
-    return _temporal_call(lambda *a: L.lib().lrt_temporal_accumulate_moving_host(ctypes.byref(d), ctypes.byref(sm), *a),
-                          color, cur, prev, out, n, check, lambda b: b.ctypes.data,
-                          lambda: np.zeros((h, w, 4), np.float32), (mp,))
+    return _temporal(B.HostBuffers(), "temporal_accumulate_moving", (d, sm), color, cur, prev, out, (motion,))
 
 
 def temporal_accumulate_moving_tensor(color, cur: dict, prev: Optional[dict], camera: L.Camera,
@@ -559,33 +543,12 @@ def temporal_accumulate_moving_tensor(color, cur: dict, prev: Optional[dict], ca
     """temporal_accumulate_moving_host on cuda float32 tensors (lrt_temporal_accumulate_moving_device):
     asynchronous on `stream` and ordered only against it; the sphere arrays are read before it
     returns. motion: a cuda tensor [height, width, 4], or None."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(color, params)
     d = temporal_desc(w, h, camera, prev_camera, **params)
     sm = _scene_motion(spheres, prev_spheres)
-    n = w * h * 4
-    if not getattr(color, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color.device)
-
-    def check(t, what):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == torch.float32
-                and t.is_contiguous() and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda float32 tensor of >= {n} elements")
-
-    def make():
-        with torch.cuda.stream(s):
-            return torch.zeros((h, w, 4), device=color.device)
-
-    if motion is not None:
-        check(motion, "motion")
-    mp = ctypes.c_void_p(motion.data_ptr()) if motion is not None else None
-    return _temporal_call(lambda *a: L.lib().lrt_temporal_accumulate_moving_device(ctypes.byref(d), ctypes.byref(sm),
-                                                                                   *a),
-                          color, cur, prev, out, n, check, lambda t: t.data_ptr(), make,
-                          (mp, ctypes.c_void_p(s.cuda_stream)))
+    bufs = B.tensor_buffers(color, "color", w * h * 4, stream)
+    return _temporal(bufs, "temporal_accumulate_moving", (d, sm), color, cur, prev, out, (motion,))
 
 
 def temporal_gbuffer_desc(width: int, height: int, **params) -> L.TemporalGbufferDesc:
@@ -593,58 +556,44 @@ def temporal_gbuffer_desc(width: int, height: int, **params) -> L.TemporalGbuffe
     normal_min, short_std, min_history overridden."""
     d = L.TemporalGbufferDesc()
     L.check(L.lib().lrt_temporal_gbuffer_default(int(width), int(height), ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.TEMPORAL_GBUFFER_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown temporal parameter {name!r}")
-        setattr(d, name, int(v) if name == "min_history" else float(v))
-    return d
+    return _override(d, params, L.TEMPORAL_GBUFFER_PARAMS, ("min_history",), "temporal")
 
 
-def _temporal_gbuffer_call(entry, color, cur, prev_g, prev, out, check, ptr, make, extra):
-    """The argument marshalling the host and tensor front ends share: check(buf, what, name)
-    validates a plane called `name` (int32 of width x height for "id", else float32 quads), ptr(buf)
-    is its address, make() a zeroed frame. Returns the new state."""
-    check(color, "color", "color")
+def _gbuffer_planes(bufs, given, what, need, kinds, stored=None) -> L.Gbuffer:
+    """lrt_gbuffer of the planes a unit reads of a G-buffer (a whole one may be passed: the rest is not
+    read): those in `stored`, by default the `need`ed ones."""
+    return _members(bufs, given, L.Gbuffer, kinds, what=what, need=need, known=L.GBUFFER_NAMES,
+                    stored=need if stored is None else stored, noun="G-buffer plane")
 
-    def planes(d, need, what):
-        if not isinstance(d, dict) or any(n not in d for n in need):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must hold " + " and ".join(need))
-        g = L.Gbuffer()
-        for name, buf in d.items():
-            if name not in L.GBUFFER_NAMES:
-                raise L.LrtError(L.LRT_E_INVALID, f"unknown G-buffer plane {name!r}")
-            if name in need:                  # a whole G-buffer may be passed as it is: the rest is not read
-                check(buf, f"{what} {name}", name)
-                setattr(g, name, ptr(buf))
-        return g
 
-    def state(d, names, what):
-        for name in L.TEMPORAL_GBUFFER_STATE_NAMES:
-            if not isinstance(d, dict) or name not in d:
-                raise L.LrtError(L.LRT_E_INVALID, f"{what} lacks {name!r}")
-        st = L.TemporalState()
-        for name, buf in d.items():
-            if name not in names:
-                raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
-            if name in L.TEMPORAL_GBUFFER_STATE_NAMES:
-                check(buf, f"{what} {name}", name)
-                setattr(st, name, ptr(buf))
-        return st
+def _gbuffer_state(bufs, given, what, known, kinds) -> L.TemporalState:
+    """lrt_temporal_state of the color and moment2 of a state of the G-buffer-driven units."""
+    return _members(bufs, given, L.TemporalState, kinds, what=what, need=L.TEMPORAL_GBUFFER_STATE_NAMES,
+                    known=known + ("color_std",), stored=L.TEMPORAL_GBUFFER_STATE_NAMES, noun="state buffer")
 
-    gc = planes(cur, L.TEMPORAL_GBUFFER_CUR_NAMES, "cur")
-    gp = planes(prev_g, L.TEMPORAL_GBUFFER_PREV_NAMES, "prev_g") if prev_g is not None else None
+
+def _new_gbuffer_state(bufs, quad) -> dict:
+    return {name: bufs.new(quad) for name in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
+
+
+def _byref(st):
+    return ctypes.byref(st) if st is not None else None
+
+
+def _temporal_gbuffer(bufs, d, color, cur, prev_g, prev, out):
+    k = _kinds(d.width, d.height)
+    quad = k["quad"]
+    bufs.check_plane(color, "color", quad)
+    gc = _gbuffer_planes(bufs, cur, "cur", L.TEMPORAL_GBUFFER_CUR_NAMES, k)
+    gp = _gbuffer_planes(bufs, prev_g, "prev_g", L.TEMPORAL_GBUFFER_PREV_NAMES, k) if prev_g is not None else None
     # (a returned state, or an accumulator's, may be passed back as it is: only color and moment2 are read)
-    ps = state(prev, L.TEMPORAL_STATE_NAMES + ("color_std",), "prev") if prev is not None else None
+    ps = _gbuffer_state(bufs, prev, "prev", L.TEMPORAL_STATE_NAMES, k) if prev is not None else None
     if out is None:
-        out = {name: make() for name in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
-    ns = state(out, L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",), "out")
-    std = None
-    if "color_std" in out:
-        check(out["color_std"], "out color_std", "color_std")
-        std = ptr(out["color_std"])
-    L.check(entry(ctypes.c_void_p(ptr(color)), ctypes.byref(gc), ctypes.byref(gp) if gp is not None else None,
-                  ctypes.byref(ps) if ps is not None else None, ctypes.byref(ns),
-                  ctypes.c_void_p(std) if std else None, *extra))
+        out = _new_gbuffer_state(bufs, quad)
+    ns = _gbuffer_state(bufs, out, "out", L.TEMPORAL_GBUFFER_STATE_NAMES, k)
+    L.check(bufs.entry("temporal_accumulate_gbuffer")(ctypes.byref(d), bufs.ptr(color), ctypes.byref(gc), _byref(gp),
+                                                      _byref(ps), ctypes.byref(ns), _color_std(bufs, out, quad),
+                                                      *bufs.tail))
     return out
 
 
@@ -663,15 +612,7 @@ def temporal_accumulate_gbuffer_host(color: np.ndarray, cur: dict, prev_g: Optio
     params = dict(params)
     w, h = _frame_size(color, params)
     d = temporal_gbuffer_desc(w, h, **params)
-
-    def check(buf, what, name):
-        n, dt = (w * h, np.int32) if name == "id" else (w * h * 4, np.float32)
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
-
-    return _temporal_gbuffer_call(lambda *a: L.lib().lrt_temporal_accumulate_gbuffer_host(ctypes.byref(d), *a), color,
-                                  cur, prev_g, prev, out, check, lambda b: b.ctypes.data,
-                                  lambda: np.zeros((h, w, 4), np.float32), ())
+    return _temporal_gbuffer(B.HostBuffers(), d, color, cur, prev_g, prev, out)
 
 
 def temporal_accumulate_gbuffer_tensor(color, cur: dict, prev_g: Optional[dict], prev: Optional[dict],
@@ -679,28 +620,11 @@ def temporal_accumulate_gbuffer_tensor(color, cur: dict, prev_g: Optional[dict],
     """temporal_accumulate_gbuffer_host on cuda tensors (lrt_temporal_accumulate_gbuffer_device):
     asynchronous on `stream` (a torch.cuda.Stream, default: current) and ordered only against it.
     "id" is an int32 tensor, the others float32. Returns the new state."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(color, params)
     d = temporal_gbuffer_desc(w, h, **params)
-    if not getattr(color, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {w * h * 4} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color.device)
-
-    def check(t, what, name):
-        n, dt = (w * h, torch.int32) if name == "id" else (w * h * 4, torch.float32)
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == dt
-                and t.is_contiguous() and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
-
-    def make():
-        with torch.cuda.stream(s):
-            return torch.zeros((h, w, 4), device=color.device)
-
-    return _temporal_gbuffer_call(lambda *a: L.lib().lrt_temporal_accumulate_gbuffer_device(ctypes.byref(d), *a),
-                                  color, cur, prev_g, prev, out, check, lambda t: t.data_ptr(), make,
-                                  (ctypes.c_void_p(s.cuda_stream),))
+    bufs = B.tensor_buffers(color, "color", w * h * 4, stream)
+    return _temporal_gbuffer(bufs, d, color, cur, prev_g, prev, out)
 
 
 # ---- history rectification -----------------------------------------------------------------
@@ -709,47 +633,26 @@ def temporal_rectify_desc(width: int, height: int, **params) -> L.RectifyDesc:
     min_history, ref_scale, gamma, range_floor, reset_history, short_std overridden."""
     d = L.RectifyDesc()
     L.check(L.lib().lrt_temporal_rectify_default(int(width), int(height), ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.RECTIFY_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown rectify parameter {name!r}")
-        setattr(d, name, int(v) if name in L.RECTIFY_INT_PARAMS else float(v))
-    return d
+    return _override(d, params, L.RECTIFY_PARAMS, L.RECTIFY_INT_PARAMS, "rectify")
 
 
-def _temporal_rectify_call(entry, ref, ids, state, out, class_out, check, ptr, make, extra):
-    """The argument marshalling the host and tensor front ends share (see _temporal_gbuffer_call).
-    Returns the rectified state."""
-    check(ref, "ref", "ref")
-    check(ids, "id", "id")
-
-    def buffers(d, names, what):
-        for name in L.TEMPORAL_GBUFFER_STATE_NAMES:
-            if not isinstance(d, dict) or name not in d:
-                raise L.LrtError(L.LRT_E_INVALID, f"{what} lacks {name!r}")
-        st = L.TemporalState()
-        for name, buf in d.items():
-            if name not in names:
-                raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
-            if name in L.TEMPORAL_GBUFFER_STATE_NAMES:
-                check(buf, f"{what} {name}", name)
-                setattr(st, name, ptr(buf))
-        return st
-
+def _temporal_rectify(bufs, d, ref, ids, state, out, class_out):
+    k = _kinds(d.width, d.height)
+    quad, word = k["quad"], k["word"]
+    bufs.check_plane(ref, "ref", quad)
+    bufs.check_plane(ids, "id", word)
     # (a returned state, or an accumulator's, may be passed as it is: only color and moment2 are read)
-    ss = buffers(state, L.TEMPORAL_STATE_NAMES + ("color_std",), "state")
+    ss = _gbuffer_state(bufs, state, "state", L.TEMPORAL_STATE_NAMES, k)
     if out is None:
-        out = {name: make() for name in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
+        out = _new_gbuffer_state(bufs, quad)
     # out=state is in place: the state's other members are left alone (its color_std, if any, is refreshed)
-    ns = buffers(out, (L.TEMPORAL_STATE_NAMES if out is state else L.TEMPORAL_GBUFFER_STATE_NAMES) + ("color_std",), "out")
-    std = cls = None
-    if "color_std" in out:
-        check(out["color_std"], "out color_std", "color_std")
-        std = ptr(out["color_std"])
+    ns = _gbuffer_state(bufs, out, "out", L.TEMPORAL_STATE_NAMES if out is state else L.TEMPORAL_GBUFFER_STATE_NAMES,
+                        k)
+    std = _color_std(bufs, out, quad)
     if class_out is not None:
-        check(class_out, "class_out", "id")
-        cls = ptr(class_out)
-    L.check(entry(ctypes.c_void_p(ptr(ref)), ctypes.c_void_p(ptr(ids)), ctypes.byref(ss), ctypes.byref(ns),
-                  ctypes.c_void_p(std) if std else None, ctypes.c_void_p(cls) if cls else None, *extra))
+        bufs.check_plane(class_out, "class_out", word)
+    L.check(bufs.entry("temporal_rectify")(ctypes.byref(d), bufs.ptr(ref), bufs.ptr(ids), ctypes.byref(ss),
+                                           ctypes.byref(ns), std, bufs.ptr(class_out), *bufs.tail))
     return out
 
 
@@ -768,14 +671,7 @@ def temporal_rectify_host(ref: np.ndarray, id: np.ndarray, state: dict, out: Opt
     params = dict(params)
     w, h = _frame_size(ref, params)
     d = temporal_rectify_desc(w, h, **params)
-
-    def check(buf, what, name):
-        n, dt = (w * h, np.int32) if name == "id" else (w * h * 4, np.float32)
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
-
-    return _temporal_rectify_call(lambda *a: L.lib().lrt_temporal_rectify_host(ctypes.byref(d), *a), ref, id, state, out,
-                                  class_out, check, lambda b: b.ctypes.data, lambda: np.zeros((h, w, 4), np.float32), ())
+    return _temporal_rectify(B.HostBuffers(), d, ref, id, state, out, class_out)
 
 
 def temporal_rectify_tensor(ref, id, state: dict, out: Optional[dict] = None, class_out=None, stream=None,
@@ -783,27 +679,11 @@ def temporal_rectify_tensor(ref, id, state: dict, out: Optional[dict] = None, cl
     """temporal_rectify_host on cuda tensors (lrt_temporal_rectify_device): asynchronous on `stream`
     (a torch.cuda.Stream, default: current) and ordered only against it. id and class_out are int32
     tensors, the others float32. Returns the rectified state."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(ref, params)
     d = temporal_rectify_desc(w, h, **params)
-    if not getattr(ref, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"ref must be a contiguous cuda float32 tensor of >= {w * h * 4} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-
-    def check(t, what, name):
-        n, dt = (w * h, torch.int32) if name == "id" else (w * h * 4, torch.float32)
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == ref.device and t.dtype == dt
-                and t.is_contiguous() and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
-
-    def make():
-        with torch.cuda.stream(s):
-            return torch.zeros((h, w, 4), device=ref.device)
-
-    return _temporal_rectify_call(lambda *a: L.lib().lrt_temporal_rectify_device(ctypes.byref(d), *a), ref, id, state,
-                                  out, class_out, check, lambda t: t.data_ptr(), make, (ctypes.c_void_p(s.cuda_stream),))
+    bufs = B.tensor_buffers(ref, "ref", w * h * 4, stream)
+    return _temporal_rectify(bufs, d, ref, id, state, out, class_out)
 
 
 class TemporalAccumulator:
@@ -982,11 +862,24 @@ def svgf_desc(width: int, height: int, **params) -> L.SvgfDesc:
     sigma_color, sigma_normal, sigma_pos, albedo_floor overridden."""
     d = L.SvgfDesc()
     L.check(L.lib().lrt_svgf_default(int(width), int(height), ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.SVGF_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown svgf parameter {name!r}")
-        setattr(d, name, int(v) if name in ("iterations", "min_history") else float(v))
-    return d
+    return _override(d, params, L.SVGF_PARAMS, ("iterations", "min_history"), "svgf")
+
+
+def _svgf_filter(bufs, d, color, moment2, guides, out, variance_out):
+    n = d.width * d.height * 4
+    bufs.check(color, "color", n)
+    bufs.check(moment2, "moment2", n)
+    if out is None:
+        out = bufs.copy(color)
+    bufs.check(out, "out", n)
+    if variance_out is not None:
+        bufs.check(variance_out, "variance_out", n)
+    # (step()'s guides may be passed as they are: color_std is not read)
+    f = _features(bufs, guides or {}, n, L.FEATURE_NAMES, "guide", stored=L.SVGF_GUIDE_NAMES)
+    L.check(bufs.entry("svgf_filter")(ctypes.byref(d), bufs.ptr(color), bufs.ptr(moment2),
+                                      ctypes.byref(f) if guides else None, bufs.ptr(out), bufs.ptr(variance_out),
+                                      *bufs.tail))
+    return out
 
 
 def svgf_filter_host(color: np.ndarray, moment2: np.ndarray, guides: Optional[dict],
@@ -1001,64 +894,17 @@ def svgf_filter_host(color: np.ndarray, moment2: np.ndarray, guides: Optional[di
     sigma_color, sigma_normal, sigma_pos, albedo_floor. Returns out."""
     params = dict(params)
     w, h = _frame_size(color, params)
-    d = svgf_desc(w, h, **params)
-    n = w * h * 4
-    _check_host_buffer(color, n)
-    _check_host_buffer(moment2, n)
-    if out is None:
-        out = color.copy()
-    _check_host_buffer(out, n)
-    if variance_out is not None:
-        _check_host_buffer(variance_out, n)
-    f = L.Features()
-    for name, buf in (guides or {}).items():
-        if name not in L.FEATURE_NAMES:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown guide {name!r}")
-        if name not in L.SVGF_GUIDE_NAMES:      # step()'s guides may be passed as they are: color_std is not read
-            continue
-        _check_host_buffer(buf, n)
-        setattr(f, name, buf.ctypes.data)
-    L.check(L.lib().lrt_svgf_filter_host(
-        ctypes.byref(d), color.ctypes.data_as(ctypes.c_void_p), moment2.ctypes.data_as(ctypes.c_void_p),
-        ctypes.byref(f) if guides else None, out.ctypes.data_as(ctypes.c_void_p),
-        variance_out.ctypes.data_as(ctypes.c_void_p) if variance_out is not None else None))
-    return out
+    return _svgf_filter(B.HostBuffers(), svgf_desc(w, h, **params), color, moment2, guides, out, variance_out)
 
 
 def svgf_filter_tensor(color, moment2, guides: Optional[dict], out=None, variance_out=None, stream=None, **params):
     """svgf_filter_host on cuda float32 tensors (lrt_svgf_filter_device): asynchronous on `stream`
     (a torch.cuda.Stream, default: current) and ordered only against it. Returns out."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(color, params)
     d = svgf_desc(w, h, **params)
-    n = w * h * 4
-    if not getattr(color, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color.device)
-
-    def ok(t):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == torch.float32
-                and t.is_contiguous() and t.numel() >= n)
-
-    if out is None:
-        with torch.cuda.stream(s):
-            out = color.clone()
-    for what, t in (("color", color), ("moment2", moment2), ("out", out), ("variance_out", variance_out)):
-        if not (ok(t) or (t is None and what == "variance_out")):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda float32 tensor of >= {n} elements")
-    unknown = [k for k in (guides or {}) if k not in L.FEATURE_NAMES]
-    if unknown:
-        raise L.LrtError(L.LRT_E_INVALID, f"unknown guide {unknown[0]!r}")
-    f = _tensor_features({k: v for k, v in (guides or {}).items() if k in L.SVGF_GUIDE_NAMES}, n,
-                         L.SVGF_GUIDE_NAMES, color.device)     # (step()'s color_std is not read)
-    L.check(L.lib().lrt_svgf_filter_device(
-        ctypes.byref(d), ctypes.c_void_p(color.data_ptr()), ctypes.c_void_p(moment2.data_ptr()),
-        ctypes.byref(f) if guides else None, ctypes.c_void_p(out.data_ptr()),
-        ctypes.c_void_p(variance_out.data_ptr()) if variance_out is not None else None,
-        ctypes.c_void_p(s.cuda_stream)))
-    return out
+    bufs = B.tensor_buffers(color, "color", w * h * 4, stream)
+    return _svgf_filter(bufs, d, color, moment2, guides, out, variance_out)
 
 
 # ---- auto-exposure metering and tone mapping -------------------------------------------------
@@ -1068,21 +914,28 @@ def tonemap_desc(width: int, height: int, **params) -> L.TonemapDesc:
     adapt, white overridden."""
     d = L.TonemapDesc()
     L.check(L.lib().lrt_tonemap_default(int(width), int(height), ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.TONEMAP_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown tonemap parameter {name!r}")
-        if name == "op" and isinstance(v, str):
-            if v not in L.TONEMAP_OPS:
-                raise L.LrtError(L.LRT_E_INVALID, f"unknown tone operator {v!r}")
-            v = L.TONEMAP_OPS[v]
-        setattr(d, name, int(v) if name in ("op", "auto_exposure") else float(v))
-    return d
+    op = params.get("op")
+    if isinstance(op, str):
+        if op not in L.TONEMAP_OPS:
+            raise L.LrtError(L.LRT_E_INVALID, f"unknown tone operator {op!r}")
+        params = dict(params, op=L.TONEMAP_OPS[op])
+    return _override(d, params, L.TONEMAP_PARAMS, ("op", "auto_exposure"), "tonemap")
 
 
-def _check_host_words(buf, n: int, what: str) -> None:
-    if not (isinstance(buf, np.ndarray) and buf.dtype in (np.uint32, np.int32) and buf.flags.c_contiguous
-            and buf.size >= n):
-        raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous uint32 array of >= {n} elements")
+def _tonemap(bufs, d, color, state, out, bgra, histogram):
+    n = d.width * d.height * 4
+    words = (bufs.uword, "int32", "uint32")       # either passes; the message names the back end's own
+    bufs.check(color, "color", n)
+    if state is None and d.auto_exposure:
+        state = bufs.zeros(4)
+    for what, buf, count, dtypes in (("state", state, 4, ("float32",)), ("out", out, n, ("float32",)),
+                                     ("bgra", bgra, d.width * d.height, words),
+                                     ("histogram", histogram, L.TONEMAP_HIST_WORDS, words)):
+        if buf is not None:
+            bufs.check(buf, what, count, dtypes)
+    L.check(bufs.entry("tonemap")(ctypes.byref(d), bufs.ptr(color), bufs.ptr(state), bufs.ptr(histogram), bufs.ptr(out),
+                                  bufs.ptr(bgra), *bufs.tail))
+    return state
 
 
 def tonemap_host(color: np.ndarray, state: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None,
@@ -1097,22 +950,7 @@ def tonemap_host(color: np.ndarray, state: Optional[np.ndarray] = None, out: Opt
     given; it is left untouched then)."""
     params = dict(params)
     w, h = _frame_size(color, params)
-    d = tonemap_desc(w, h, **params)
-    n = w * h * 4
-    _check_host_buffer(color, n)
-    if state is None and d.auto_exposure:
-        state = np.zeros(4, np.float32)
-    if state is not None:
-        _check_host_buffer(state, 4)
-    if out is not None:
-        _check_host_buffer(out, n)
-    if bgra is not None:
-        _check_host_words(bgra, w * h, "bgra")
-    if histogram is not None:
-        _check_host_words(histogram, L.TONEMAP_HIST_WORDS, "histogram")
-    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
-    L.check(L.lib().lrt_tonemap_host(ctypes.byref(d), ptr(color), ptr(state), ptr(histogram), ptr(out), ptr(bgra)))
-    return state
+    return _tonemap(B.HostBuffers(), tonemap_desc(w, h, **params), color, state, out, bgra, histogram)
 
 
 def tonemap_tensor(color, state=None, out=None, bgra=None, histogram=None, stream=None, **params):
@@ -1120,34 +958,11 @@ def tonemap_tensor(color, state=None, out=None, bgra=None, histogram=None, strea
     torch.cuda.Stream, default: current) and ordered only against it; the exposure never visits
     the host. color, out: float32; state: float32 of >= 4; bgra, histogram: int32 (or uint32).
     Returns the state tensor."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(color, params)
     d = tonemap_desc(w, h, **params)
-    n = w * h * 4
-    if not getattr(color, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {n} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color.device)
-    words = tuple(t for t in (torch.int32, getattr(torch, "uint32", None)) if t is not None)
-
-    def ok(t, dtypes, count):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype in dtypes
-                and t.is_contiguous() and t.numel() >= count)
-
-    if state is None and d.auto_exposure:
-        with torch.cuda.stream(s):
-            state = torch.zeros(4, device=color.device)
-    for what, t, dtypes, count in (("color", color, (torch.float32,), n), ("state", state, (torch.float32,), 4),
-                                   ("out", out, (torch.float32,), n), ("bgra", bgra, words, w * h),
-                                   ("histogram", histogram, words, L.TONEMAP_HIST_WORDS)):
-        if not (ok(t, dtypes, count) or (t is None and what != "color")):
-            kind = "float32" if dtypes == (torch.float32,) else "int32"
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {kind} tensor of >= {count} elements")
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    L.check(L.lib().lrt_tonemap_device(ctypes.byref(d), ptr(color), ptr(state), ptr(histogram), ptr(out), ptr(bgra),
-                                       ctypes.c_void_p(s.cuda_stream)))
-    return state
+    bufs = B.tensor_buffers(color, "color", w * h * 4, stream)
+    return _tonemap(bufs, d, color, state, out, bgra, histogram)
 
 
 class ToneMapper:
@@ -1203,24 +1018,27 @@ def gbuffer_desc(width: int, height: int, camera: L.Camera, prev_camera: Optiona
     return d
 
 
-def _gbuffer_call(entry, width, height, out, want, make, ptr, check, spheres, prev_spheres, extra):
-    """The marshalling the host and tensor front ends share. out: the caller's planes {name: buffer}
-    (only those are written), or None for new ones: the three guides and whatever `want` names.
-    make(name) is a new plane, ptr(buf) its address, check(buf, name) validates one."""
+def _out_tensor_buffers(out, kinds, device, stream):
+    """The TensorBuffers of a unit that keys on its output planes: on the device of out's first plane,
+    or on `device` where it allocates them."""
+    if not out:
+        return B.TensorBuffers(device, stream)
+    name, first = next(iter(out.items()))
+    count, dtypes, _ = kinds.get(name, kinds["quad"])
+    return B.tensor_buffers(first, name, count, stream, dtypes[0])
+
+
+def _new_planes(bufs, names, kinds) -> dict:
+    return {name: bufs.new(kinds.get(name, kinds["quad"])) for name in names}
+
+
+def _gbuffer(bufs, d, out, want, spheres, prev_spheres):
+    """out: the caller's planes {name: buffer} (only those are written), or None for new ones."""
+    k = _kinds(d.width, d.height)
     if out is None:
-        out = {name: make(name) for name in L.GBUFFER_GUIDE_NAMES + tuple(n for n in L.GBUFFER_EXTRA_NAMES if want[n])}
-    g = L.Gbuffer()
-    for name, buf in out.items():
-        if name not in L.GBUFFER_NAMES:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown G-buffer plane {name!r}")
-        check(buf, name)
-        setattr(g, name, ptr(buf))
-    sm = None
-    if prev_spheres is not None:
-        sm = _scene_motion(spheres if spheres is not None else get_scene()[0], prev_spheres)
-    elif spheres is not None:
-        raise L.LrtError(L.LRT_E_INVALID, "spheres needs prev_spheres")
-    L.check(entry(ctypes.byref(sm) if sm is not None else None, ctypes.byref(g), *extra))
+        out = _new_planes(bufs, L.GBUFFER_GUIDE_NAMES + tuple(n for n in L.GBUFFER_EXTRA_NAMES if want[n]), k)
+    g = _gbuffer_planes(bufs, out, "", (), k, stored=L.GBUFFER_NAMES)
+    L.check(bufs.entry("gbuffer")(ctypes.byref(d), _moved(spheres, prev_spheres), ctypes.byref(g), *bufs.tail))
     return out
 
 
@@ -1238,21 +1056,7 @@ def gbuffer_host(width: int, height: int, camera: L.Camera, prev_camera: Optiona
     out: the caller's planes instead, any subset of the six names; only those are written."""
     w, h = int(width), int(height)
     d = gbuffer_desc(w, h, camera, prev_camera, guide_scale)
-
-    def make(name):
-        if name == "id":
-            return np.zeros((h, w), np.int32)
-        return np.zeros((h, w) if name == "depth" else (h, w, 4), np.float32)
-
-    def check(buf, name):
-        n = w * h * (1 if name in ("id", "depth") else 4)
-        dt = np.int32 if name == "id" else np.float32
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
-            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
-
-    return _gbuffer_call(lambda *a: L.lib().lrt_gbuffer_host(ctypes.byref(d), *a), w, h, out,
-                         dict(id=id, depth=depth, motion=motion), make, lambda b: b.ctypes.data, check,
-                         spheres, prev_spheres, ())
+    return _gbuffer(B.HostBuffers(), d, out, dict(id=id, depth=depth, motion=motion), spheres, prev_spheres)
 
 
 def gbuffer_tensor(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera] = None,
@@ -1261,29 +1065,10 @@ def gbuffer_tensor(width: int, height: int, camera: L.Camera, prev_camera: Optio
     """gbuffer_host into cuda tensors (lrt_gbuffer_device): asynchronous on `stream` (a
     torch.cuda.Stream, default: current) and ordered only against it; the sphere arrays are read
     before it returns. "id" is an int32 tensor, the others float32."""
-    import torch
-
     w, h = int(width), int(height)
     d = gbuffer_desc(w, h, camera, prev_camera, guide_scale)
-    dev = next(iter(out.values())).device if out else torch.device(device)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-
-    def make(name):
-        with torch.cuda.stream(s):
-            if name == "id":
-                return torch.zeros((h, w), dtype=torch.int32, device=dev)
-            return torch.zeros((h, w) if name == "depth" else (h, w, 4), device=dev)
-
-    def check(t, name):
-        n = w * h * (1 if name in ("id", "depth") else 4)
-        dt = torch.int32 if name == "id" else torch.float32
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()
-                and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a contiguous cuda {dt} tensor of >= {n} elements")
-
-    return _gbuffer_call(lambda *a: L.lib().lrt_gbuffer_device(ctypes.byref(d), *a), w, h, out,
-                         dict(id=id, depth=depth, motion=motion), make, lambda t: t.data_ptr(), check,
-                         spheres, prev_spheres, (ctypes.c_void_p(s.cuda_stream),))
+    bufs = _out_tensor_buffers(out, _kinds(w, h), device, stream)
+    return _gbuffer(bufs, d, out, dict(id=id, depth=depth, motion=motion), spheres, prev_spheres)
 
 
 # ---- G-buffer chain: guides and path keys through mirrors and glass -------------------------
@@ -1301,21 +1086,21 @@ def gbuffer_chain_desc(width: int, height: int, camera: L.Camera, max_bounces: i
     return d
 
 
-def _gbuffer_chain_call(entry, out, which, make, ptr, check, extra):
-    """The marshalling the host and tensor front ends share. out: the caller's planes {name: buffer}
-    (only those are written), or None for new ones: all seven but those `which` sets False."""
+def _chain_kinds(width: int, height: int):
+    return _kinds(width, height, words=L.GBUFFER_CHAIN_INT_NAMES)
+
+
+def _gbuffer_chain(bufs, d, out, which):
+    """which: name=False leaves a plane out of the new ones."""
     for name in which:
         if name not in L.GBUFFER_CHAIN_NAMES:
             raise L.LrtError(L.LRT_E_INVALID, f"unknown chain plane {name!r}")
+    k = _chain_kinds(d.width, d.height)
     if out is None:
-        out = {name: make(name) for name in L.GBUFFER_CHAIN_NAMES if which.get(name, True)}
-    g = L.GbufferChain()
-    for name, buf in out.items():
-        if name not in L.GBUFFER_CHAIN_NAMES:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown chain plane {name!r}")
-        check(buf, name)
-        setattr(g, name, ptr(buf))
-    L.check(entry(ctypes.byref(g), *extra))
+        out = _new_planes(bufs, [name for name in L.GBUFFER_CHAIN_NAMES if which.get(name, True)], k)
+    g = _members(bufs, out, L.GbufferChain, k, known=L.GBUFFER_CHAIN_NAMES, stored=L.GBUFFER_CHAIN_NAMES,
+                 noun="chain plane")
+    L.check(bufs.entry("gbuffer_chain")(ctypes.byref(d), ctypes.byref(g), *bufs.tail))
     return out
 
 
@@ -1341,22 +1126,7 @@ def gbuffer_chain_host(width: int, height: int, camera: L.Camera, max_bounces: i
       upsample_tensor with "key" as "id" in both G-buffers."""
     w, h = int(width), int(height)
     d = gbuffer_chain_desc(w, h, camera, max_bounces, roughness_max, guide_scale)
-
-    def kind(name):
-        return (1, np.int32) if name in L.GBUFFER_CHAIN_INT_NAMES else (1 if name == "depth" else 4, np.float32)
-
-    def make(name):
-        k, dt = kind(name)
-        return np.zeros((h, w) if k == 1 else (h, w, 4), dt)
-
-    def check(buf, name):
-        k, dt = kind(name)
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < w * h * k:
-            raise L.LrtError(L.LRT_E_INVALID,
-                             f"{name} must be a C-contiguous {np.dtype(dt).name} array of >= {w * h * k} elements")
-
-    return _gbuffer_chain_call(lambda *a: L.lib().lrt_gbuffer_chain_host(ctypes.byref(d), *a), out, which, make,
-                               lambda b: b.ctypes.data, check, ())
+    return _gbuffer_chain(B.HostBuffers(), d, out, which)
 
 
 def gbuffer_chain_tensor(width: int, height: int, camera: L.Camera, max_bounces: int = 4, roughness_max: float = 0.25,
@@ -1365,29 +1135,9 @@ def gbuffer_chain_tensor(width: int, height: int, camera: L.Camera, max_bounces:
     """gbuffer_chain_host into cuda tensors (lrt_gbuffer_chain_device): asynchronous on `stream` (a
     torch.cuda.Stream, default: current) and ordered only against it. "key", "id" and "bounces" are
     int32 tensors, the others float32. The composition is gbuffer_chain_host's."""
-    import torch
-
     w, h = int(width), int(height)
     d = gbuffer_chain_desc(w, h, camera, max_bounces, roughness_max, guide_scale)
-    dev = next(iter(out.values())).device if out else torch.device(device)
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-
-    def kind(name):
-        return (1, torch.int32) if name in L.GBUFFER_CHAIN_INT_NAMES else (1 if name == "depth" else 4, torch.float32)
-
-    def make(name):
-        k, dt = kind(name)
-        with torch.cuda.stream(s):
-            return torch.zeros((h, w) if k == 1 else (h, w, 4), dtype=dt, device=dev)
-
-    def check(t, name):
-        k, dt = kind(name)
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()
-                and t.numel() >= w * h * k):
-            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a contiguous cuda {dt} tensor of >= {w * h * k} elements")
-
-    return _gbuffer_chain_call(lambda *a: L.lib().lrt_gbuffer_chain_device(ctypes.byref(d), *a), out, which, make,
-                               lambda t: t.data_ptr(), check, (ctypes.c_void_p(s.cuda_stream),))
+    return _gbuffer_chain(_out_tensor_buffers(out, _chain_kinds(w, h), device, stream), d, out, which)
 
 
 # ---- G-buffer chain motion: motion vectors inside mirrors and glass -------------------------
@@ -1402,31 +1152,18 @@ def gbuffer_chain_motion_desc(width: int, height: int, camera: L.Camera, prev_ca
     L.check(L.lib().lrt_gbuffer_chain_motion_default(int(width), int(height), ctypes.byref(camera),
                                                      ctypes.byref(prev_camera) if prev_camera is not None else None,
                                                      ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.GBUFFER_CHAIN_MOTION_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown chain motion parameter {name!r}")
-        setattr(d, name, int(v) if name in ("max_bounces", "iterations") else float(v))
-    return d
+    return _override(d, params, L.GBUFFER_CHAIN_MOTION_PARAMS, ("max_bounces", "iterations"), "chain motion")
 
 
-def _gbuffer_chain_motion_call(entry, first_motion, out, want, make, ptr, check, spheres, prev_spheres, extra):
-    """The marshalling the host and tensor front ends share. out: the caller's planes {name: buffer}
-    (only those are written), or None for new ones: those `want` names."""
+def _gbuffer_chain_motion(bufs, d, first_motion, out, want, spheres, prev_spheres):
+    k = _kinds(d.width, d.height, words=("status",))
     if out is None:
-        out = {name: make(name) for name in L.GBUFFER_CHAIN_MOTION_NAMES if want[name]}
-    g = L.GbufferChainMotion()
-    for name, buf in out.items():
-        if name not in L.GBUFFER_CHAIN_MOTION_NAMES:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown chain motion plane {name!r}")
-        check(buf, name)
-        setattr(g, name, ptr(buf))
-    check(first_motion, "first_motion")
-    sm = None
-    if prev_spheres is not None:
-        sm = _scene_motion(spheres if spheres is not None else get_scene()[0], prev_spheres)
-    elif spheres is not None:
-        raise L.LrtError(L.LRT_E_INVALID, "spheres needs prev_spheres")
-    L.check(entry(ctypes.byref(sm) if sm is not None else None, ctypes.c_void_p(ptr(first_motion)), ctypes.byref(g), *extra))
+        out = _new_planes(bufs, [name for name in L.GBUFFER_CHAIN_MOTION_NAMES if want[name]], k)
+    g = _members(bufs, out, L.GbufferChainMotion, k, known=L.GBUFFER_CHAIN_MOTION_NAMES,
+                 stored=L.GBUFFER_CHAIN_MOTION_NAMES, noun="chain motion plane")
+    bufs.check_plane(first_motion, "first_motion", k["quad"])
+    L.check(bufs.entry("gbuffer_chain_motion")(ctypes.byref(d), _moved(spheres, prev_spheres), bufs.ptr(first_motion),
+                                               ctypes.byref(g), *bufs.tail))
     return out
 
 
@@ -1451,23 +1188,8 @@ def gbuffer_chain_motion_host(width: int, height: int, camera: L.Camera, prev_ca
     and likewise "motion" of temporal_upsample_* and temporal_rectify_*."""
     w, h = int(width), int(height)
     d = gbuffer_chain_motion_desc(w, h, camera, prev_camera, **params)
-
-    def kind(name):
-        return (1, np.int32) if name == "status" else (4, np.float32)
-
-    def make(name):
-        k, dt = kind(name)
-        return np.zeros((h, w) if k == 1 else (h, w, 4), dt)
-
-    def check(buf, name):
-        k, dt = kind(name)
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < w * h * k:
-            raise L.LrtError(L.LRT_E_INVALID,
-                             f"{name} must be a C-contiguous {np.dtype(dt).name} array of >= {w * h * k} elements")
-
-    return _gbuffer_chain_motion_call(lambda *a: L.lib().lrt_gbuffer_chain_motion_host(ctypes.byref(d), *a),
-                                      first_motion, out, dict(motion=motion, status=status), make,
-                                      lambda b: b.ctypes.data, check, spheres, prev_spheres, ())
+    return _gbuffer_chain_motion(B.HostBuffers(), d, first_motion, out, dict(motion=motion, status=status), spheres,
+                                 prev_spheres)
 
 
 def gbuffer_chain_motion_tensor(width: int, height: int, camera: L.Camera, prev_camera: Optional[L.Camera],
@@ -1476,33 +1198,10 @@ def gbuffer_chain_motion_tensor(width: int, height: int, camera: L.Camera, prev_
     """gbuffer_chain_motion_host on cuda tensors (lrt_gbuffer_chain_motion_device): asynchronous on
     `stream` (a torch.cuda.Stream, default: current) and ordered only against it; the sphere arrays are
     read before it returns. "status" is an int32 tensor, "motion" float32, on first_motion's device."""
-    import torch
-
     w, h = int(width), int(height)
     d = gbuffer_chain_motion_desc(w, h, camera, prev_camera, **params)
-    if not isinstance(first_motion, torch.Tensor) or not first_motion.is_cuda:
-        raise L.LrtError(L.LRT_E_INVALID, "first_motion must be a cuda tensor")
-    dev = first_motion.device
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
-
-    def kind(name):
-        return (1, torch.int32) if name == "status" else (4, torch.float32)
-
-    def make(name):
-        k, dt = kind(name)
-        with torch.cuda.stream(s):
-            return torch.zeros((h, w) if k == 1 else (h, w, 4), dtype=dt, device=dev)
-
-    def check(t, name):
-        k, dt = kind(name)
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()
-                and t.numel() >= w * h * k):
-            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a contiguous cuda {dt} tensor of >= {w * h * k} elements")
-
-    return _gbuffer_chain_motion_call(lambda *a: L.lib().lrt_gbuffer_chain_motion_device(ctypes.byref(d), *a),
-                                      first_motion, out, dict(motion=motion, status=status), make,
-                                      lambda t: t.data_ptr(), check, spheres, prev_spheres,
-                                      (ctypes.c_void_p(s.cuda_stream),))
+    bufs = B.tensor_buffers(first_motion, "first_motion", w * h * 4, stream)
+    return _gbuffer_chain_motion(bufs, d, first_motion, out, dict(motion=motion, status=status), spheres, prev_spheres)
 
 
 # ---- G-buffer-guided upsampling of a low-resolution frame -----------------------------------
@@ -1511,11 +1210,7 @@ def upsample_desc(width: int, height: int, low_width: int, low_height: int, **pa
     sigma_normal, albedo_floor, weight_min, flags (UP_BILINEAR) overridden."""
     d = L.UpsampleDesc()
     L.check(L.lib().lrt_upsample_default(int(width), int(height), int(low_width), int(low_height), ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.UPSAMPLE_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown upsample parameter {name!r}")
-        setattr(d, name, int(v) if name == "flags" else float(v))
-    return d
+    return _override(d, params, L.UPSAMPLE_PARAMS, ("flags",), "upsample")
 
 
 def _upsample_sizes(color_low, low, high):
@@ -1531,31 +1226,19 @@ def _upsample_sizes(color_low, low, high):
     return int(high["id"].shape[1]), int(high["id"].shape[0]), int(color_low.shape[1]), int(color_low.shape[0])
 
 
-def _upsample_call(entry, d, color_low, low, high, out, class_out, check, ptr, extra):
-    """The marshalling the host and tensor front ends share: check(buf, what, name, low) validates a
-    plane called `name` of the low or the output frame (int32 for "id" and "class", else float32
-    quads), ptr(buf) is its address."""
+def _upsample(bufs, d, color_low, low, high, out, class_out):
+    k, kl = _kinds(d.width, d.height), _kinds(d.low_width, d.low_height)
     need = ("id",) if d.flags & L.UP_BILINEAR else ("id", "normal")
-    check(color_low, "color_low", "color", True)
-
-    def planes(g, what, is_low):
-        if any(n not in g for n in need):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must hold " + " and ".join(need))
-        s = L.Gbuffer()
-        for name, buf in g.items():
-            if name not in L.GBUFFER_NAMES:
-                raise L.LrtError(L.LRT_E_INVALID, f"unknown G-buffer plane {name!r}")
-            if name in L.UPSAMPLE_NAMES:      # a whole G-buffer may be passed as it is: the rest is not read
-                check(buf, f"{what} {name}", name, is_low)
-                setattr(s, name, ptr(buf))
-        return s
-
-    gl, gh = planes(low, "low", True), planes(high, "high", False)
-    check(out, "out", "out", False)
+    bufs.check_plane(color_low, "color_low", kl["quad"])
+    gl = _gbuffer_planes(bufs, low, "low", need, kl, stored=L.UPSAMPLE_NAMES)
+    gh = _gbuffer_planes(bufs, high, "high", need, k, stored=L.UPSAMPLE_NAMES)
+    if out is None:
+        out = bufs.new(k["quad"])
+    bufs.check_plane(out, "out", k["quad"])
     if class_out is not None:
-        check(class_out, "class_out", "class", False)
-    L.check(entry(ctypes.c_void_p(ptr(color_low)), ctypes.byref(gl), ctypes.byref(gh), ctypes.c_void_p(ptr(out)),
-                  ctypes.c_void_p(ptr(class_out)) if class_out is not None else None, *extra))
+        bufs.check_plane(class_out, "class_out", k["word"])
+    L.check(bufs.entry("upsample")(ctypes.byref(d), bufs.ptr(color_low), ctypes.byref(gl), ctypes.byref(gh),
+                                   bufs.ptr(out), bufs.ptr(class_out), *bufs.tail))
     return out
 
 
@@ -1573,43 +1256,17 @@ def upsample_host(color_low: np.ndarray, low: dict, high: dict, out: Optional[np
     albedo_floor, weight_min, flags (UP_BILINEAR: every pixel class 2, no normals needed). Returns out."""
     w, h, lw, lh = _upsample_sizes(color_low, low, high)
     d = upsample_desc(w, h, lw, lh, **params)
-    if out is None:
-        out = np.zeros((h, w, 4), np.float32)
-
-    def check(buf, what, name, is_low):
-        n = (lw * lh if is_low else w * h) * (1 if name in ("id", "class") else 4)
-        dt = np.int32 if name in ("id", "class") else np.float32
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
-
-    return _upsample_call(lambda *a: L.lib().lrt_upsample_host(ctypes.byref(d), *a), d, color_low, low, high, out,
-                          class_out, check, lambda b: b.ctypes.data, ())
+    return _upsample(B.HostBuffers(), d, color_low, low, high, out, class_out)
 
 
 def upsample_tensor(color_low, low: dict, high: dict, out=None, class_out=None, stream=None, **params):
     """upsample_host on cuda tensors (lrt_upsample_device): asynchronous on `stream` (a
     torch.cuda.Stream, default: current) and ordered only against it. "id" and class_out are int32
     tensors, the others float32. Returns out."""
-    import torch
-
     w, h, lw, lh = _upsample_sizes(color_low, low, high)
     d = upsample_desc(w, h, lw, lh, **params)
-    if not getattr(color_low, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color_low must be a contiguous cuda float32 tensor of >= {lw * lh * 4} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color_low.device)
-    if out is None:
-        with torch.cuda.stream(s):
-            out = torch.zeros((h, w, 4), device=color_low.device)
-
-    def check(t, what, name, is_low):
-        n = (lw * lh if is_low else w * h) * (1 if name in ("id", "class") else 4)
-        dt = torch.int32 if name in ("id", "class") else torch.float32
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color_low.device and t.dtype == dt
-                and t.is_contiguous() and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
-
-    return _upsample_call(lambda *a: L.lib().lrt_upsample_device(ctypes.byref(d), *a), d, color_low, low, high, out,
-                          class_out, check, lambda t: t.data_ptr(), (ctypes.c_void_p(s.cuda_stream),))
+    bufs = B.tensor_buffers(color_low, "color_low", lw * lh * 4, stream)
+    return _upsample(bufs, d, color_low, low, high, out, class_out)
 
 
 # ---- temporal upsampling: a full-resolution history from jittered low frames -----------------
@@ -1620,11 +1277,7 @@ def temporal_upsample_desc(width: int, height: int, low_width: int, low_height: 
     d = L.TemporalUpsampleDesc()
     L.check(L.lib().lrt_temporal_upsample_default(int(width), int(height), int(low_width), int(low_height),
                                                   ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.TEMPORAL_UPSAMPLE_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown temporal upsample parameter {name!r}")
-        setattr(d, name, int(v) if name in ("min_history", "jitter_x", "jitter_y") else float(v))
-    return d
+    return _override(d, params, L.TEMPORAL_UPSAMPLE_PARAMS, ("min_history", "jitter_x", "jitter_y"), "temporal upsample")
 
 
 def jitter_camera(camera: L.Camera, width: int, height: int, low_width: int, low_height: int, jitter_x: int,
@@ -1663,54 +1316,23 @@ def _temporal_upsample_sizes(color_low, cur):
     return int(cur["id"].shape[1]), int(cur["id"].shape[0]), int(color_low.shape[1]), int(color_low.shape[0])
 
 
-def _temporal_upsample_call(entry, color_low, low, cur, prev_g, prev, out, class_out, check, ptr, make, extra):
-    """The marshalling the host and tensor front ends share: check(buf, what, name, is_low) validates
-    a plane called `name` of the low or the output frame (int32 for "id" and "class", else float32
-    quads), ptr(buf) is its address, make() a zeroed output frame. Returns the new state."""
-    check(color_low, "color_low", "color", True)
-
-    def planes(d, need, what, is_low):
-        if not isinstance(d, dict) or any(n not in d for n in need):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must hold " + " and ".join(need))
-        g = L.Gbuffer()
-        for name, buf in d.items():
-            if name not in L.GBUFFER_NAMES:
-                raise L.LrtError(L.LRT_E_INVALID, f"unknown G-buffer plane {name!r}")
-            if name in need:                  # a whole G-buffer may be passed as it is: the rest is not read
-                check(buf, f"{what} {name}", name, is_low)
-                setattr(g, name, ptr(buf))
-        return g
-
-    def state(d, names, what):
-        for name in L.TEMPORAL_GBUFFER_STATE_NAMES:
-            if not isinstance(d, dict) or name not in d:
-                raise L.LrtError(L.LRT_E_INVALID, f"{what} lacks {name!r}")
-        st = L.TemporalState()
-        for name, buf in d.items():
-            if name not in names:
-                raise L.LrtError(L.LRT_E_INVALID, f"unknown state buffer {name!r}")
-            if name in L.TEMPORAL_GBUFFER_STATE_NAMES:
-                check(buf, f"{what} {name}", name, False)
-                setattr(st, name, ptr(buf))
-        return st
-
-    gl = planes(low, L.TEMPORAL_UPSAMPLE_LOW_NAMES, "low", True)
-    gc = planes(cur, L.TEMPORAL_GBUFFER_CUR_NAMES, "cur", False)
-    gp = planes(prev_g, L.TEMPORAL_GBUFFER_PREV_NAMES, "prev_g", False) if prev_g is not None else None
-    ps = state(prev, L.TEMPORAL_STATE_NAMES + ("color_std",), "prev") if prev is not None else None
+def _temporal_upsample(bufs, d, color_low, low, cur, prev_g, prev, out, class_out):
+    k, kl = _kinds(d.width, d.height), _kinds(d.low_width, d.low_height)
+    quad = k["quad"]
+    bufs.check_plane(color_low, "color_low", kl["quad"])
+    gl = _gbuffer_planes(bufs, low, "low", L.TEMPORAL_UPSAMPLE_LOW_NAMES, kl)
+    gc = _gbuffer_planes(bufs, cur, "cur", L.TEMPORAL_GBUFFER_CUR_NAMES, k)
+    gp = _gbuffer_planes(bufs, prev_g, "prev_g", L.TEMPORAL_GBUFFER_PREV_NAMES, k) if prev_g is not None else None
+    ps = _gbuffer_state(bufs, prev, "prev", L.TEMPORAL_STATE_NAMES, k) if prev is not None else None
     if out is None:
-        out = {name: make() for name in L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",)}
-    ns = state(out, L.TEMPORAL_GBUFFER_STATE_NAMES + ("color_std",), "out")
-    std = None
-    if "color_std" in out:
-        check(out["color_std"], "out color_std", "color_std", False)
-        std = ptr(out["color_std"])
+        out = _new_gbuffer_state(bufs, quad)
+    ns = _gbuffer_state(bufs, out, "out", L.TEMPORAL_GBUFFER_STATE_NAMES, k)
+    std = _color_std(bufs, out, quad)
     if class_out is not None:
-        check(class_out, "class_out", "class", False)
-    L.check(entry(ctypes.c_void_p(ptr(color_low)), ctypes.byref(gl), ctypes.byref(gc),
-                  ctypes.byref(gp) if gp is not None else None, ctypes.byref(ps) if ps is not None else None,
-                  ctypes.byref(ns), ctypes.c_void_p(std) if std else None,
-                  ctypes.c_void_p(ptr(class_out)) if class_out is not None else None, *extra))
+        bufs.check_plane(class_out, "class_out", k["word"])
+    L.check(bufs.entry("temporal_upsample")(ctypes.byref(d), bufs.ptr(color_low), ctypes.byref(gl), ctypes.byref(gc),
+                                            _byref(gp), _byref(ps), ctypes.byref(ns), std, bufs.ptr(class_out),
+                                            *bufs.tail))
     return out
 
 
@@ -1731,16 +1353,7 @@ def temporal_upsample_host(color_low: np.ndarray, low: dict, cur: dict, prev_g: 
     new state (out)."""
     w, h, lw, lh = _temporal_upsample_sizes(color_low, cur)
     d = temporal_upsample_desc(w, h, lw, lh, jitter_x=jitter[0], jitter_y=jitter[1], **params)
-
-    def check(buf, what, name, is_low):
-        n = (lw * lh if is_low else w * h) * (1 if name in ("id", "class") else 4)
-        dt = np.int32 if name in ("id", "class") else np.float32
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
-
-    return _temporal_upsample_call(lambda *a: L.lib().lrt_temporal_upsample_host(ctypes.byref(d), *a), color_low, low,
-                                   cur, prev_g, prev, out, class_out, check, lambda b: b.ctypes.data,
-                                   lambda: np.zeros((h, w, 4), np.float32), ())
+    return _temporal_upsample(B.HostBuffers(), d, color_low, low, cur, prev_g, prev, out, class_out)
 
 
 def temporal_upsample_tensor(color_low, low: dict, cur: dict, prev_g: Optional[dict], prev: Optional[dict],
@@ -1748,28 +1361,10 @@ def temporal_upsample_tensor(color_low, low: dict, cur: dict, prev_g: Optional[d
     """temporal_upsample_host on cuda tensors (lrt_temporal_upsample_device): asynchronous on `stream`
     (a torch.cuda.Stream, default: current) and ordered only against it. "id" and class_out are int32
     tensors, the others float32. Returns the new state."""
-    import torch
-
     w, h, lw, lh = _temporal_upsample_sizes(color_low, cur)
     d = temporal_upsample_desc(w, h, lw, lh, jitter_x=jitter[0], jitter_y=jitter[1], **params)
-    if not getattr(color_low, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color_low must be a contiguous cuda float32 tensor of >= {lw * lh * 4} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color_low.device)
-
-    def check(t, what, name, is_low):
-        n = (lw * lh if is_low else w * h) * (1 if name in ("id", "class") else 4)
-        dt = torch.int32 if name in ("id", "class") else torch.float32
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color_low.device and t.dtype == dt
-                and t.is_contiguous() and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
-
-    def make():
-        with torch.cuda.stream(s):
-            return torch.zeros((h, w, 4), device=color_low.device)
-
-    return _temporal_upsample_call(lambda *a: L.lib().lrt_temporal_upsample_device(ctypes.byref(d), *a), color_low, low,
-                                   cur, prev_g, prev, out, class_out, check, lambda t: t.data_ptr(), make,
-                                   (ctypes.c_void_p(s.cuda_stream),))
+    bufs = B.tensor_buffers(color_low, "color_low", lw * lh * 4, stream)
+    return _temporal_upsample(bufs, d, color_low, low, cur, prev_g, prev, out, class_out)
 
 
 class TemporalUpsampler:
@@ -1856,11 +1451,23 @@ def sample_budget_desc(width: int, height: int, min_count: int, max_count: int, 
     d = L.SampleBudgetDesc()
     L.check(L.lib().lrt_sample_budget_default(int(width), int(height), int(min_count), int(max_count), int(budget),
                                               ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.SAMPLE_BUDGET_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown sample budget parameter {name!r}")
-        setattr(d, name, int(v) if name in ("flags", "passes") else float(v))
-    return d
+    return _override(d, params, L.SAMPLE_BUDGET_PARAMS, ("flags", "passes"), "sample budget")
+
+
+def _sample_budget(bufs, d, variance, color, counts, info, info_dtype: str):
+    """info: two 64-bit words (the host's own uint64 pair, the caller's int64 tensor), or None."""
+    k = B.planes(d.width, d.height)
+    bufs.check_plane(variance, "variance", k["quad"])
+    if color is not None:
+        bufs.check_plane(color, "color", k["quad"])
+    if counts is None:
+        counts = bufs.new(k["word"])
+    bufs.check_plane(counts, "counts", k["word"])
+    if info is not None:
+        bufs.check(info, "info", 2, (info_dtype,))
+    L.check(bufs.entry("sample_budget")(ctypes.byref(d), bufs.ptr(variance), bufs.ptr(color), bufs.ptr(counts),
+                                        bufs.ptr(info), *bufs.tail))
+    return counts
 
 
 def sample_budget_host(variance: np.ndarray, min_count: int, max_count: int, budget: int,
@@ -1874,15 +1481,8 @@ def sample_budget_host(variance: np.ndarray, min_count: int, max_count: int, bud
     params = dict(params)
     w, h = _frame_size(variance, params)
     d = sample_budget_desc(w, h, min_count, max_count, budget, **params)
-    _check_host_buffer(variance, w * h * 4)
-    if color is not None:
-        _check_host_buffer(color, w * h * 4)
-    if counts is None:
-        counts = np.zeros((h, w), np.int32)
-    _check_host_counts(counts, w * h)
     info = np.zeros(2, np.uint64)
-    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None   # noqa: E731
-    L.check(L.lib().lrt_sample_budget_host(ctypes.byref(d), ptr(variance), ptr(color), ptr(counts), ptr(info)))
+    counts = _sample_budget(B.HostBuffers(), d, variance, color, counts, info, "uint64")
     return counts, (int(info[0]), int(info[1]))
 
 
@@ -1892,32 +1492,11 @@ def sample_budget_tensor(variance, min_count: int, max_count: int, budget: int, 
     torch.cuda.Stream, default: current) and ordered only against it; nothing visits the host.
     variance, color: float32; counts: int32 of >= width * height (default a new [height, width]
     tensor); info: int64 of >= 2, or None. Returns counts."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(variance, params)
     d = sample_budget_desc(w, h, min_count, max_count, budget, **params)
-    n = w * h * 4
-    if not getattr(variance, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"variance must be a contiguous cuda float32 tensor of >= {n} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(variance.device)
-
-    def ok(t, dtype, count):
-        return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == variance.device and t.dtype == dtype
-                and t.is_contiguous() and t.numel() >= count)
-
-    if counts is None:
-        with torch.cuda.stream(s):
-            counts = torch.zeros((h, w), dtype=torch.int32, device=variance.device)
-    for what, t, dtype, count in (("variance", variance, torch.float32, n), ("color", color, torch.float32, n),
-                                  ("counts", counts, torch.int32, w * h), ("info", info, torch.int64, 2)):
-        if not (ok(t, dtype, count) or (t is None and what in ("color", "info"))):
-            kind = str(dtype).replace("torch.", "")
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {kind} tensor of >= {count} elements")
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    L.check(L.lib().lrt_sample_budget_device(ctypes.byref(d), ptr(variance), ptr(color), ptr(counts), ptr(info),
-                                             ctypes.c_void_p(s.cuda_stream)))
-    return counts
+    bufs = B.tensor_buffers(variance, "variance", w * h * 4, stream)
+    return _sample_budget(bufs, d, variance, color, counts, info, "int64")
 
 
 def _render_counts(d: L.RenderDesc, counts_ptr, capacity, mean: bool, info_ptr, total_cap: int) -> L.RenderCounts:
@@ -1939,8 +1518,8 @@ def render_counts_host(job: Job, backbuffer: np.ndarray, counts: np.ndarray, cap
     values. Returns (rays, info) with info = (samples traced, pixels skipped)."""
     d = job.desc()
     npix = d.row_count * d.x_count
-    _check_host_buffer(backbuffer, npix * 4)
-    _check_host_counts(counts, npix, exact=True)
+    B.HostBuffers().check(backbuffer, "backbuffer", npix * 4)
+    B.HostBuffers().check(counts, "counts", npix, ("int32",), exact=True)
     info = np.zeros(2, np.uint64)
     rc = _render_counts(d, counts.ctypes.data, capacity, mean, info.ctypes.data, npix * d.frames)
     rays = ctypes.c_longlong(0)
@@ -1959,23 +1538,17 @@ def render_counts_tensor(job: Job, buf, rays, counts, capacity: Optional[int], m
 
     d = job.desc()
     npix = d.row_count * d.x_count
-    need = npix * 4
-    if not (getattr(buf, "is_cuda", False) and buf.dtype == torch.float32 and buf.is_contiguous()
-            and buf.numel() >= need):
-        raise L.LrtError(L.LRT_E_INVALID, f"buf must be a contiguous cuda float32 tensor of >= {need} elements")
+    bufs = B.tensor_buffers(buf, "buf", npix * 4, stream)
+    bufs.check(buf, "buf", npix * 4)
     if not (getattr(rays, "is_cuda", False) and rays.dtype == torch.int64 and rays.numel() >= 1):
         raise L.LrtError(L.LRT_E_INVALID, "rays must be a cuda int64 tensor")
-    if not (getattr(counts, "is_cuda", False) and counts.device == buf.device and counts.dtype == torch.int32
-            and counts.is_contiguous() and counts.numel() == npix):
-        raise L.LrtError(L.LRT_E_INVALID, f"counts must be a contiguous cuda int32 tensor of {npix} elements")
-    if info is not None and not (getattr(info, "is_cuda", False) and info.device == buf.device
-                                 and info.dtype == torch.int64 and info.is_contiguous() and info.numel() >= 2):
-        raise L.LrtError(L.LRT_E_INVALID, "info must be a contiguous cuda int64 tensor of >= 2 elements")
-    s = stream if stream is not None else torch.cuda.current_stream(buf.device)
+    bufs.check(counts, "counts", npix, ("int32",), exact=True)
+    if info is not None:
+        bufs.check(info, "info", 2, ("int64",))
     rc = _render_counts(d, counts.data_ptr(), capacity, mean, info.data_ptr() if info is not None else None,
                         npix * d.frames)
-    L.check(L.lib().lrt_render_counts_device(ctypes.byref(d), ctypes.byref(rc), ctypes.c_void_p(buf.data_ptr()),
-                                             ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(s.cuda_stream)))
+    L.check(L.lib().lrt_render_counts_device(ctypes.byref(d), ctypes.byref(rc), bufs.ptr(buf),
+                                             ctypes.c_void_p(rays.data_ptr()), *bufs.tail))
 
 
 # ---- firefly suppression ---------------------------------------------------------------------
@@ -1984,30 +1557,26 @@ def firefly_desc(width: int, height: int, **params) -> L.FireflyDesc:
     floor overridden."""
     d = L.FireflyDesc()
     L.check(L.lib().lrt_firefly_default(int(width), int(height), ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.FIREFLY_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown firefly parameter {name!r}")
-        setattr(d, name, int(v) if name in L.FIREFLY_INT_PARAMS else float(v))
-    return d
+    return _override(d, params, L.FIREFLY_PARAMS, L.FIREFLY_INT_PARAMS, "firefly")
 
 
-def _firefly_call(entry, color, ids, out, excess_out, class_out, info, check, ptr, make, extra) -> dict:
-    """The argument marshalling the host and tensor front ends share: check(buf, what, kind)
-    validates a buffer ("quad": float32 quads, "word": int32 per pixel, "info": two 32-bit words),
-    ptr(buf) is its address, make(kind) a new zeroed buffer. An optional output given as True is
-    allocated. Returns {"out"[, "excess"][, "class"][, "info"]}."""
-    check(color, "color", "quad")
+def _firefly(bufs, d, color, ids, out, excess_out, class_out, info) -> dict:
+    """An optional output given as True is allocated. Returns {"out"[, "excess"][, "class"][, "info"]}."""
+    k = B.planes(d.width, d.height)
+    k["info"] = (2, (bufs.uword,), (2,))   # the two counts: uint32 on the host, an int32 tensor
+    bufs.check_plane(color, "color", k["quad"])
     if ids is not None:
-        check(ids, "id", "word")
-    res = {"out": make("quad") if out is None else out}
+        bufs.check_plane(ids, "id", k["word"])
+    res = {"out": bufs.new(k["quad"]) if out is None else out}
     for name, buf, kind in (("excess", excess_out, "quad"), ("class", class_out, "word"), ("info", info, "info")):
         if buf is not None and buf is not False:
-            res[name] = make(kind) if buf is True else buf
+            res[name] = bufs.new(k[kind]) if buf is True else buf
     for name, kind in (("out", "quad"), ("excess", "quad"), ("class", "word"), ("info", "info")):
         if name in res:
-            check(res[name], name if name == "out" or name == "info" else f"{name}_out", kind)
-    p = lambda b: ctypes.c_void_p(ptr(b)) if b is not None else None   # noqa: E731
-    L.check(entry(p(color), p(ids), p(res["out"]), p(res.get("excess")), p(res.get("class")), p(res.get("info")), *extra))
+            bufs.check_plane(res[name], name if name == "out" or name == "info" else f"{name}_out", k[kind])
+    L.check(bufs.entry("firefly")(ctypes.byref(d), bufs.ptr(color), bufs.ptr(ids), bufs.ptr(res["out"]),
+                                  bufs.ptr(res.get("excess")), bufs.ptr(res.get("class")), bufs.ptr(res.get("info")),
+                                  *bufs.tail))
     return res
 
 
@@ -2025,15 +1594,7 @@ def firefly_host(color: np.ndarray, id: Optional[np.ndarray] = None, out: Option
     params = dict(params)
     w, h = _frame_size(color, params)
     d = firefly_desc(w, h, **params)
-    kinds = {"quad": (w * h * 4, np.float32, (h, w, 4)), "word": (w * h, np.int32, (h, w)), "info": (2, np.uint32, (2,))}
-
-    def check(buf, what, kind):
-        n, dt, _ = kinds[kind]
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
-
-    return _firefly_call(lambda *a: L.lib().lrt_firefly_host(ctypes.byref(d), *a), color, id, out, excess_out, class_out,
-                         info, check, lambda b: b.ctypes.data, lambda kind: np.zeros(kinds[kind][2], kinds[kind][1]), ())
+    return _firefly(B.HostBuffers(), d, color, id, out, excess_out, class_out, info)
 
 
 def firefly_tensor(color, id=None, out=None, excess_out=None, class_out=None, info=None, stream=None, **params) -> dict:
@@ -2041,29 +1602,11 @@ def firefly_tensor(color, id=None, out=None, excess_out=None, class_out=None, in
     torch.cuda.Stream, default: current) and ordered only against it; nothing visits the host. id
     and class_out are int32 tensors, info an int32 tensor of >= 2 elements (the two counts), the
     others float32. Returns {"out"[, "excess"][, "class"][, "info"]}."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(color, params)
     d = firefly_desc(w, h, **params)
-    if not getattr(color, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {w * h * 4} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color.device)
-    kinds = {"quad": (w * h * 4, torch.float32, (h, w, 4)), "word": (w * h, torch.int32, (h, w)),
-             "info": (2, torch.int32, (2,))}
-
-    def check(t, what, kind):
-        n, dt, _ = kinds[kind]
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == dt
-                and t.is_contiguous() and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
-
-    def make(kind):
-        with torch.cuda.stream(s):
-            return torch.zeros(kinds[kind][2], dtype=kinds[kind][1], device=color.device)
-
-    return _firefly_call(lambda *a: L.lib().lrt_firefly_device(ctypes.byref(d), *a), color, id, out, excess_out,
-                         class_out, info, check, lambda t: t.data_ptr(), make, (ctypes.c_void_p(s.cuda_stream),))
+    bufs = B.tensor_buffers(color, "color", w * h * 4, stream)
+    return _firefly(bufs, d, color, id, out, excess_out, class_out, info)
 
 
 # ---- firefly restore ---------------------------------------------------------------------------
@@ -2071,11 +1614,21 @@ def firefly_restore_desc(width: int, height: int, **params) -> L.FireflyRestoreD
     """lrt_firefly_restore_default for a width x height frame, with radius overridden if given."""
     d = L.FireflyRestoreDesc()
     L.check(L.lib().lrt_firefly_restore_default(int(width), int(height), ctypes.byref(d)))
-    for name, v in params.items():
-        if name not in L.FIREFLY_RESTORE_PARAMS:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown firefly restore parameter {name!r}")
-        setattr(d, name, int(v))
-    return d
+    return _override(d, params, L.FIREFLY_RESTORE_PARAMS, L.FIREFLY_RESTORE_PARAMS, "firefly restore")
+
+
+def _firefly_restore(bufs, d, color, excess, ids, out) -> dict:
+    k = B.planes(d.width, d.height)
+    bufs.check_plane(color, "color", k["quad"])
+    bufs.check_plane(excess, "excess", k["quad"])
+    if ids is not None:
+        bufs.check_plane(ids, "id", k["word"])
+    if out is None:
+        out = bufs.new(k["quad"])
+    bufs.check_plane(out, "out", k["quad"])
+    L.check(bufs.entry("firefly_restore")(ctypes.byref(d), bufs.ptr(color), bufs.ptr(excess), bufs.ptr(ids),
+                                          bufs.ptr(out), *bufs.tail))
+    return {"out": out}
 
 
 def firefly_restore_host(color: np.ndarray, excess: np.ndarray, id: Optional[np.ndarray] = None,
@@ -2088,80 +1641,14 @@ def firefly_restore_host(color: np.ndarray, excess: np.ndarray, id: Optional[np.
     Returns {"out"}."""
     params = dict(params)
     w, h = _frame_size(color, params)
-    d = firefly_restore_desc(w, h, **params)
-    kinds = {"quad": (w * h * 4, np.float32), "word": (w * h, np.int32)}
-
-    def check(buf, what, kind):
-        n, dt = kinds[kind]
-        if not isinstance(buf, np.ndarray) or buf.dtype != dt or not buf.flags.c_contiguous or buf.size < n:
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a C-contiguous {np.dtype(dt).name} array of >= {n} elements")
-
-    check(color, "color", "quad")
-    check(excess, "excess", "quad")
-    if id is not None:
-        check(id, "id", "word")
-    if out is None:
-        out = np.zeros((h, w, 4), np.float32)
-    check(out, "out", "quad")
-    p = lambda b: ctypes.c_void_p(b.ctypes.data) if b is not None else None   # noqa: E731
-    L.check(L.lib().lrt_firefly_restore_host(ctypes.byref(d), p(color), p(excess), p(id), p(out)))
-    return {"out": out}
+    return _firefly_restore(B.HostBuffers(), firefly_restore_desc(w, h, **params), color, excess, id, out)
 
 
 def firefly_restore_tensor(color, excess, id=None, out=None, stream=None, **params) -> dict:
     """firefly_restore_host on cuda tensors (lrt_firefly_restore_device): asynchronous on `stream` (a
     torch.cuda.Stream, default: current) and ordered only against it; nothing visits the host. id is
     an int32 tensor, the others float32; out=color means in place. Returns {"out"}."""
-    import torch
-
     params = dict(params)
     w, h = _frame_size(color, params)
     d = firefly_restore_desc(w, h, **params)
-    if not getattr(color, "is_cuda", False):
-        raise L.LrtError(L.LRT_E_INVALID, f"color must be a contiguous cuda float32 tensor of >= {w * h * 4} elements")
-    s = stream if stream is not None else torch.cuda.current_stream(color.device)
-
-    def check(t, what, n, dt):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == color.device and t.dtype == dt
-                and t.is_contiguous() and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{what} must be a contiguous cuda {dt} tensor of >= {n} elements")
-
-    check(color, "color", w * h * 4, torch.float32)
-    check(excess, "excess", w * h * 4, torch.float32)
-    if id is not None:
-        check(id, "id", w * h, torch.int32)
-    if out is None:
-        with torch.cuda.stream(s):
-            out = torch.zeros((h, w, 4), dtype=torch.float32, device=color.device)
-    check(out, "out", w * h * 4, torch.float32)
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    L.check(L.lib().lrt_firefly_restore_device(ctypes.byref(d), p(color), p(excess), p(id), p(out),
-                                               ctypes.c_void_p(s.cuda_stream)))
-    return {"out": out}
-
-
-def _check_host_counts(buf, n: int, exact: bool = False) -> None:
-    if not (isinstance(buf, np.ndarray) and buf.dtype == np.int32 and buf.flags.c_contiguous
-            and (buf.size == n if exact else buf.size >= n)):
-        raise L.LrtError(L.LRT_E_INVALID,
-                         f"counts must be a C-contiguous int32 array of {'' if exact else '>= '}{n} elements")
-
-
-def _tensor_features(tensors: dict, n: int, names, device) -> L.Features:
-    """lrt_features over cuda float32 tensors of >= n elements, keyed by its member names."""
-    import torch
-
-    f = L.Features()
-    for name, t in tensors.items():
-        if name not in names:
-            raise L.LrtError(L.LRT_E_INVALID, f"unknown feature {name!r}")
-        if not (t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous()
-                and t.numel() >= n):
-            raise L.LrtError(L.LRT_E_INVALID, f"{name} must be a contiguous cuda float32 tensor of >= {n} elements")
-        setattr(f, name, t.data_ptr())
-    return f
-
-
-def _check_host_buffer(buf: np.ndarray, n: int) -> None:
-    if not isinstance(buf, np.ndarray) or buf.dtype != np.float32 or not buf.flags.c_contiguous or buf.size < n:
-        raise L.LrtError(L.LRT_E_INVALID, f"backbuffer must be a C-contiguous float32 array of >= {n} elements")
+    return _firefly_restore(B.tensor_buffers(color, "color", w * h * 4, stream), d, color, excess, id, out)

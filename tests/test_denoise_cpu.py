@@ -90,6 +90,59 @@ def test_python_front_end_rejects_bad_arguments():
         denoise_host(color, {"normal": np.zeros((9, 16, 3), np.float32)})
 
 
+def test_front_end_message_names_the_offending_argument():
+    """The checks the front ends share name the argument that failed, whichever unit it reached."""
+    from learnraytracing_amd import LrtError, denoise_host, svgf_filter_host
+    color = np.zeros((9, 16, 4), np.float32)
+    with pytest.raises(LrtError) as e:
+        denoise_host(color, None, out=np.zeros((9, 16, 4), np.float64))
+    assert e.value.code == L.LRT_E_INVALID and "out must be" in str(e.value) and "float32" in str(e.value)
+    with pytest.raises(LrtError) as e:
+        denoise_host(color, {"albedo": color[:8]})
+    assert e.value.code == L.LRT_E_INVALID and "albedo must be" in str(e.value) and ">= 576" in str(e.value)
+    with pytest.raises(LrtError) as e:
+        svgf_filter_host(color, color.copy(), None, variance_out=color[:, :, :3])
+    assert e.value.code == L.LRT_E_INVALID and "variance_out must be" in str(e.value)
+
+
+def test_every_tensor_front_end_rejects_a_host_array():
+    """A NumPy array where a post-process *_tensor front end keys on a cuda tensor is LRT_E_INVALID, before
+    any use of the device: not an AttributeError, and never a pointer handed to the library."""
+    import learnraytracing_amd as lrt
+    w, h = 16, 9
+    q, low = np.zeros((h, w, 4), np.float32), np.zeros((5, 8, 4), np.float32)
+    ids, low_ids = np.zeros((h, w), np.int32), np.zeros((5, 8), np.int32)
+    cam = lrt.default_camera(w, h)
+    g = {"normal": q, "motion": q, "id": ids}
+    gl = {"normal": low, "id": low_ids}
+    job = lrt.Job(width=w, height=h)
+    calls = {
+        "denoise": lambda: lrt.denoise_tensor(q, None),
+        "temporal_accumulate": lambda: lrt.temporal_accumulate_tensor(q, {"normal": q, "world_pos": q}, None, cam),
+        "temporal_accumulate_moving": lambda: lrt.temporal_accumulate_moving_tensor(
+            q, {"normal": q, "world_pos": q}, None, cam, None, [[0, 0, 0, 1]], [[0, 0, 0, 1]]),
+        "temporal_accumulate_gbuffer": lambda: lrt.temporal_accumulate_gbuffer_tensor(q, g, None, None),
+        "temporal_rectify": lambda: lrt.temporal_rectify_tensor(q, ids, {"color": q, "moment2": q}),
+        "svgf_filter": lambda: lrt.svgf_filter_tensor(q, q, None),
+        "tonemap": lambda: lrt.tonemap_tensor(q),
+        "gbuffer": lambda: lrt.gbuffer_tensor(w, h, cam, out={"normal": q}),
+        "gbuffer_chain": lambda: lrt.gbuffer_chain_tensor(w, h, cam, out={"key": ids}),
+        "gbuffer_chain_motion": lambda: lrt.gbuffer_chain_motion_tensor(w, h, cam, None, q),
+        "upsample": lambda: lrt.upsample_tensor(low, gl, g),
+        "temporal_upsample": lambda: lrt.temporal_upsample_tensor(low, gl, g, None, None),
+        "sample_budget": lambda: lrt.sample_budget_tensor(q, 1, 8, 600),
+        "render_counts": lambda: lrt.render_counts_tensor(job, q, np.zeros(1, np.int64), ids, None),
+        "firefly": lambda: lrt.firefly_tensor(q, ids),
+        "firefly_restore": lambda: lrt.firefly_restore_tensor(q, q, ids),
+    }
+    assert sorted(n + "_tensor" for n in calls) == sorted(
+        n for n in dir(lrt) if n.endswith("_tensor") and n != "render_tensor")
+    for name, call in calls.items():
+        with pytest.raises(lrt.LrtError) as e:
+            call()
+        assert e.value.code == L.LRT_E_INVALID and "cuda" in str(e.value), name
+
+
 def test_filter_quality_on_reference_render():
     """The specified filter earns its place: on the oracle's 160x90, 4 spp, depth 8 render with
     features, the f64 restatement with the defaults brings the MSE against the 1024 spp render to
